@@ -185,6 +185,46 @@ def usable_cores(cap=64):
     return max(1, min(n, cap))
 
 
+DUMP_BUDGET = 64 << 20          # bytes, all of --dump-outputs together
+DUMP_FEATURE_BYTES = 16 << 20   # per feature array: larger batches are dumped as a fixed, seeded sample of rows
+DUMP_PER_TENSOR = 4096          # elements sampled (fixed seed) from each parameter and its gradient
+
+
+def dump_outputs(out_dir, captured, named_params):
+    """--dump-outputs: what the timed path computed in its last step, as a caller of it receives it - the loss, the logit scale,
+    the image / text features the loss was taken on, and each parameter after the optimizer step with the gradient that step
+    applied (fixed, seeded samples where the whole would exceed DUMP_BUDGET) - as DIR/<name>.npy in float32 / float64.
+    Returns {name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator(device="cpu").manual_seed(0)
+    arrays = {"loss": captured["loss"].detach().double().reshape(1).cpu().numpy(),
+              "logit_scale": captured["logit_scale"].detach().double().reshape(1).cpu().numpy()}
+    for name in ("image_features", "text_features"):
+        f = captured[name].detach()
+        rows = max(1, min(f.shape[0], DUMP_FEATURE_BYTES // (4 * f[0].numel())))
+        if rows < f.shape[0]:
+            f = f[torch.randperm(f.shape[0], generator=g)[:rows].sort().values.to(f.device)]
+        arrays[name] = f.float().cpu().numpy()
+    params, grads, index = [], [], []
+    for n, p in named_params:
+        k = min(p.numel(), DUMP_PER_TENSOR)
+        idx = torch.randperm(p.numel(), generator=g)[:k].sort().values if k < p.numel() else torch.arange(k)
+        params.append(p.detach().reshape(-1)[idx.to(p.device)].float().cpu())
+        grads.append(p.grad.detach().reshape(-1)[idx.to(p.device)].float().cpu() if p.grad is not None else
+                     torch.full((k,), float("nan")))
+        index.append(idx.double())
+    arrays["param_sample"] = torch.cat(params).numpy()
+    arrays["grad_sample"] = torch.cat(grads).numpy()
+    arrays["sample_index"] = torch.cat(index).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise RuntimeError(f"--dump-outputs: {total} bytes over the {DUMP_BUDGET} byte budget")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def cpu_baseline(cfg, S, ctx, sample_pairs, threads):
     """The CPU port of the reference path (oracle/clip_oracle.py, fp32, torch CPU ops) on the host cores:
     forward + loss + backward + AdamW on a bounded sample of the same workload."""
@@ -326,7 +366,12 @@ def main():
                          "precision; create_model(precision='fp8')) by a child `bench.py --precision fp8` with this many timed steps and "
                          "reported as `fp8_same_workload`, never part of `value` (0 = skip)")
     ap.add_argument("--fp8-line-timeout", type=int, default=300)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (loss, logit scale, features, sampled "
+                         "parameters and gradients) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if (args.gpus > 1 or os.environ.get("CLIPA_BENCH_FORCE_DIST") == "1") and "WORLD_SIZE" not in os.environ:
         # no launcher around us: become one (same arguments, one rank per GPU); never returns.  (CLIPA_BENCH_FORCE_DIST=1: the
@@ -432,12 +477,14 @@ def main():
             lens_cache[key] = (tx.argmax(-1) + 1).cpu().tolist()      # a list: DDP moves tensor arguments of forward to the device
         return lens_cache[key]
 
-    def step(images=images, texts=texts):
+    def step(images=images, texts=texts, capture=None):
         opt.zero_grad(set_to_none=True)                        # (the sharded optimizer zeroes its flat buffers instead)
         if A == 1:
             out = step_model(images, texts, text_lengths=host_lengths(texts))
             loss = loss_fn(**out, output_dict=True)["contrastive_loss"]
             loss.backward()
+            if capture is not None:
+                capture.update(out, loss=loss)
         else:
             # training/train.py:216-256: cache every micro-batch's features without grad, then re-forward each micro-batch
             # with grad, splice its features into the cached lists, take the FULL-batch loss and back-propagate
@@ -460,6 +507,8 @@ def main():
                     inputs = {k: torch.cat(v[:j] + [o[k]] + v[j + 1:]) for k, v in feats.items()}
                     loss = loss_fn(**inputs, logit_scale=scale, output_dict=True)["contrastive_loss"]
                     loss.backward()
+                    if capture is not None and j == A - 1:
+                        capture.update(inputs, logit_scale=scale, loss=loss)
         opt.step()                                             # AdamW + logit_scale clamp, multi-tensor kernels
         return loss
 
@@ -661,13 +710,14 @@ def main():
             loss_mod.wait_timing_start()
         ops.profile_start(detail=args.shapes)
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            loss = step()
+        for i in range(args.steps):
+            loss = step(capture=captured if (args.dump_outputs and i == args.steps - 1) else None)
         fence()
         return time.perf_counter() - t0, ops.profile_stop(), loss
 
     # (single process: should the allocator run out INSIDE the warm-up / timed steps after the trial steps got through - it has
     # not happened - the plan backs off once more and the region starts over; `value` is always a complete region of K steps)
+    captured = {}                       # --dump-outputs: what the last timed step computed
     for region_attempt in range(3):
         try:
             elapsed, prof, loss = timed_region()
@@ -693,6 +743,9 @@ def main():
     if not math.isfinite(last_loss):
         print(f"bench.py: non-finite loss {last_loss}", file=sys.stderr)
         sys.exit(3)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, captured, list(model.named_parameters()))
     # the same step without the ~1100 HIP events per step that feed `roofline` / `kernels` (clipa_amd.ops.profile_start):
     # quantifies what the instrumentation costs the timed region.  Never part of `value`.
     plain_ms = None
@@ -869,6 +922,7 @@ def main():
         line = {
             "metric": "image-text pairs/sec (whole job), full training step",
             "value": round(pairs_s, 2), "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            **({"dump_outputs": {"dir": args.dump_outputs, "arrays": dumped}} if dumped is not None else {}),
             "ms_per_step": round(ms, 2), "uninstrumented_ms_per_step": plain_ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "fp8" if args.precision == "fp8" else "bf16", "data": "synthetic",
             "config": {"workload": f"{args.model}@{args.image_size} + text-{args.ctx}, local batch {B}, "

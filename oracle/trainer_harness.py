@@ -227,3 +227,74 @@ def restated_train_one_epoch(model, batches, loss, optimizer, scheduler, args, a
             accum_images, accum_texts, accum_features = [], [], {}                  # train.py:281-282
         with torch.no_grad():                                                       # train.py:285-286
             getattr(model, "module", model).logit_scale.clamp_(0, math.log(100))
+
+
+class LoopTrace:
+    """Records the loop-level operations of one train_one_epoch run, in order: model.train, scheduler, model forward, loss,
+    backward, zero_grad, clip_grad_norm_, optimizer.step and the logit-scale clamp - each with the grad / autocast state it ran
+    under and, for the forward, digests of its (normalised) images and token ids.  Nothing numeric beyond those exact inputs,
+    so a trace is the same on every host; oracle/make_live_golden.py stores the reference loop's trace for
+    tests/test_trainer_cpu.py to hold the restated loop to."""
+
+    def __init__(self):
+        self.events = []
+        self.in_backward = False
+
+    def log(self, name, *extra):
+        state = f"grad={int(torch.is_grad_enabled())} autocast={int(torch.is_autocast_enabled('cpu'))}"
+        self.events.append(" ".join([name, state] + [str(e) for e in extra]))
+
+    @staticmethod
+    def digest(t):
+        import hashlib
+        t = t.detach().cpu().contiguous()
+        return f"{str(t.dtype)[6:]}{list(t.shape)}:{hashlib.sha256(t.numpy().tobytes()).hexdigest()[:16]}"
+
+    def attach(self, model, loss, optimizer, scheduler):
+        """Instruments `model` and `optimizer` in place; returns (loss, scheduler) wrapped.  Use inside `with trace.patched():`."""
+        train = model.train
+        model.train = lambda *a: (self.log("train", *a), train(*a))[1]
+        model.register_forward_pre_hook(lambda mod, args: self.log("forward", *(self.digest(a) for a in args)))
+        for name in ("zero_grad", "step"):
+            fn = getattr(optimizer, name)
+            setattr(optimizer, name, (lambda n, f: lambda *a, **k: (self.log(n), f(*a, **k))[1])(name, fn))
+        clamp = model.logit_scale.clamp_
+        model.logit_scale.clamp_ = lambda *a: (self.log("clamp", *a), clamp(*a))[1]
+
+        def traced_loss(**k):
+            self.log("loss", *(f"{n}:{list(v.shape)}:rg={int(v.requires_grad)}" for n, v in sorted(k.items())
+                               if isinstance(v, torch.Tensor)), *(f"{n}={v}" for n, v in sorted(k.items()) if not isinstance(v, torch.Tensor)))
+            return loss(**k)
+
+        def traced_scheduler(step):
+            self.log("scheduler", step)
+            return scheduler(step)
+        return traced_loss, traced_scheduler
+
+    def patched(self):
+        import contextlib
+        trace = self
+
+        @contextlib.contextmanager
+        def ctx():
+            backward, clip = torch.Tensor.backward, torch.nn.utils.clip_grad_norm_
+
+            def traced_backward(t, *a, **k):
+                if trace.in_backward:                     # the engine's own backward calls inside the loop's (recompute)
+                    return backward(t, *a, **k)
+                trace.log("backward", list(t.shape))
+                trace.in_backward = True
+                try:
+                    return backward(t, *a, **k)
+                finally:
+                    trace.in_backward = False
+
+            def traced_clip(params, max_norm, *a, **k):
+                trace.log("clip_grad_norm_", max_norm, *a, *(f"{n}={v}" for n, v in sorted(k.items())))
+                return clip(params, max_norm, *a, **k)
+            torch.Tensor.backward, torch.nn.utils.clip_grad_norm_ = traced_backward, traced_clip
+            try:
+                yield trace
+            finally:
+                torch.Tensor.backward, torch.nn.utils.clip_grad_norm_ = backward, clip
+        return ctx()

@@ -1,12 +1,14 @@
 """CPU tests (no GPU): the oracle restatement is pinned against the golden vectors generated from the
-real reference (oracle/make_golden.py), and - when /root/reference is mounted - against the live
-reference modules."""
+real reference (oracle/make_golden.py, oracle/make_live_golden.py)."""
+import json
+import os
+
 import numpy as np
-import pytest
 import torch
 
 from oracle import clip_oracle as O
-from oracle import ref_loader
+
+from .conftest import GOLDEN
 
 
 def _oracle_run(g, dtype=torch.float32):
@@ -98,7 +100,7 @@ def test_emulated_bf16_oracle_is_close_to_fp32(golden):
 def test_dist_loss_golden():
     """Reference ClipLoss under a real 2-rank gloo group == single-process restatement on the concatenated
     batch (all four local_loss x gather_with_grad variants)."""
-    z = np.load("tests/golden/dist_loss_w2.npz")
+    z = np.load(os.path.join(GOLDEN, "dist_loss_w2.npz"))
     W, B = int(z["world"]), int(z["B"])
     s0 = float(z["logit_scale"])
     for local_loss in (True, False):
@@ -139,22 +141,19 @@ def test_dist_loss_golden():
                 assert np.allclose(gt.numpy(), z[f"gt_{key}_r{r}"], atol=2e-6), (key, r)
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason="/root/reference not mounted")
 def test_oracle_matches_live_reference_bf16_weights():
-    """Extra pin where the reference is importable: a fresh random init of the reference model."""
-    ref_model, ref_loss, _ = ref_loader.load()
-    cfg = {"embed_dim": 64,
-           "vision_cfg": {"image_size": 64, "layers": 2, "width": 128, "patch_size": 16},
-           "text_cfg": {"context_length": 12, "vocab_size": 300, "width": 128, "heads": 2, "layers": 2}}
-    torch.manual_seed(5)
-    m = ref_model.CLIP(**cfg, output_dict=True).float()
-    sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    """Extra pin on weights initialised as the reference initialises them: per tensor its constants and its uniform / normal
+    draws at its scales (the recipe of a fresh reference init, seed 5), rounded to bf16, and the reference's features and loss
+    on those weights (tests/golden/ref_init_bf16.npz, oracle/make_live_golden.py)."""
+    from oracle.make_live_golden import weights_from_recipe
+    z = np.load(os.path.join(GOLDEN, "ref_init_bf16.npz"), allow_pickle=False)
+    cfg = json.loads(str(z["cfg"]))
+    sd = weights_from_recipe(json.loads(str(z["recipe"])))
     img_u8, txt = O.synthetic_batch(6, 64, 12, 300, 3)
     images = O.normalize_images(img_u8)
-    out = m(images, txt)
-    i, t, s = O.clip_forward(sd, O.oracle_cfg(cfg), images, txt)
-    assert torch.allclose(i, out["image_features"], atol=3e-6)
-    assert torch.allclose(t, out["text_features"], atol=3e-6)
-    ref = ref_loss.ClipLoss()(out["image_features"], out["text_features"], out["logit_scale"])
-    mine, _ = O.clip_loss(i, t, s)
-    assert abs(float(ref) - float(mine)) < 1e-5
+    with torch.no_grad():
+        i, t, s = O.clip_forward(sd, O.oracle_cfg(cfg), images, txt)
+        mine, _ = O.clip_loss(i, t, s)
+    assert torch.allclose(i, torch.from_numpy(z["image_features"]), atol=3e-6)
+    assert torch.allclose(t, torch.from_numpy(z["text_features"]), atol=3e-6)
+    assert abs(float(z["loss"]) - float(mine)) < 1e-5

@@ -1,12 +1,15 @@
-"""The reference's OWN trainer drives the engine (INTEGRATION.md section 1 applied for real).
+"""The reference's trainer loop drives the engine.
 
-`training.train.train_one_epoch` (clipa_torch/training/train.py:158-314) is imported from /root/reference with `open_clip`
-bound to `clipa_amd` (oracle/trainer_harness.py) and run, unmodified, on the engine with the torch-CPU stand-in ops:
-`--precision amp_bf16` with a REAL active autocast context (the CPU flavour of train.py:160's `get_autocast`, since
-`torch.cuda.amp.autocast` switches itself off without CUDA), `--to-float-on-device`, clip_grad_norm_, AdamW groups by name,
-accum_freq 1 and 2.  Compared with tests/golden/train_loop_ref.npz = the same trainer driving the reference's own CLIP (fp32).
-Also pins the restated loop that tests/test_trainer_gpu.py uses on the GPU box (no /root/reference there) bit for bit.
+The loop of `training.train.train_one_epoch` (clipa_torch/training/train.py:158-314), as oracle/trainer_harness.py restates it,
+runs on the engine with the torch-CPU stand-in ops: `--precision amp_bf16` with a REAL active autocast context (the CPU
+flavour of train.py:160's `get_autocast`, since `torch.cuda.amp.autocast` switches itself off without CUDA),
+`--to-float-on-device`, clip_grad_norm_, AdamW groups by name, accum_freq 1 and 2.  Compared with
+tests/golden/train_loop_ref.npz = the reference's own trainer driving the reference's own CLIP (fp32).  The restated loop -
+also the one tests/test_trainer_gpu.py runs - is held operation for operation to the trace of the reference's own
+train_one_epoch driving the engine (tests/golden/train_loop_trace.npz, oracle/make_live_golden.py).
 """
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -14,14 +17,14 @@ import torch
 import clipa_amd
 from clipa_amd import engine, loss as loss_mod, model as model_mod, optim as optim_mod
 from oracle import clip_oracle as O
-from oracle import ref_loader
 from oracle import trainer_harness as H
 from oracle.make_golden import CASES
 
 from . import cpu_ops
+from .conftest import GOLDEN
 
-pytestmark = pytest.mark.skipif(not ref_loader.available(), reason="/root/reference not mounted")
-Z = np.load("tests/golden/train_loop_ref.npz")
+Z = np.load(os.path.join(GOLDEN, "train_loop_ref.npz"))
+TRACES = np.load(os.path.join(GOLDEN, "train_loop_trace.npz"))
 
 
 @pytest.fixture(autouse=True)
@@ -49,22 +52,24 @@ def _engine_and_data(accum, nsteps):
     return m, sd0, batches, H.make_args("cpu", batch_size=B, accum_freq=accum)
 
 
-def _run_reference_trainer(accum, nsteps):
-    train = H.load_trainer("engine")
-    import open_clip
-    assert open_clip.CLIP is clipa_amd.CLIP and train.CLIP is clipa_amd.CLIP
-    train.get_autocast = lambda precision: _cpu_autocast          # an ACTIVE bf16 autocast around model(...) and loss(...)
+def _run_loop(accum, nsteps, trace=None):
+    """One epoch of the restated train_one_epoch on the engine; with `trace`, under that H.LoopTrace."""
     m, sd0, batches, args = _engine_and_data(accum, nsteps)
     opt = H.make_optimizer(m)
     sched = H.make_scheduler(opt)
     loss = H.LossRecorder(clipa_amd.ClipLoss(local_loss=False, gather_with_grad=False, cache_labels=True, rank=0, world_size=1))
-    train.train_one_epoch(m, {"train": H.DataInfo(H.ListLoader(batches))}, loss, 0, opt, None, sched, None, args)
+    if trace is None:
+        H.restated_train_one_epoch(m, batches, loss, opt, sched, args, _cpu_autocast)
+    else:
+        traced_loss, traced_sched = trace.attach(m, loss, opt, sched)
+        with trace.patched():
+            H.restated_train_one_epoch(m, batches, traced_loss, opt, traced_sched, args, _cpu_autocast)
     return m, sd0, loss.values
 
 
 @pytest.mark.parametrize("tag,accum,nsteps", [("a1", 1, 3), ("a2", 2, 2)])
 def test_reference_train_one_epoch_drives_the_engine(tag, accum, nsteps):
-    m, sd0, losses = _run_reference_trainer(accum, nsteps)
+    m, sd0, losses = _run_loop(accum, nsteps)
     ref = Z[f"{tag}_losses"]
     assert len(losses) == len(ref)
     for a, b in zip(losses, ref):
@@ -87,12 +92,9 @@ def test_reference_train_one_epoch_drives_the_engine(tag, accum, nsteps):
 
 @pytest.mark.parametrize("accum,nsteps", [(1, 2), (2, 1)])
 def test_restated_loop_equals_reference_loop(accum, nsteps):
-    """The loop tests/test_trainer_gpu.py runs on the GPU box is the reference's, operation for operation."""
-    m, _, losses = _run_reference_trainer(accum, nsteps)
-    m2, _, batches, args = _engine_and_data(accum, nsteps)
-    opt = H.make_optimizer(m2)
-    loss = H.LossRecorder(clipa_amd.ClipLoss(local_loss=False, gather_with_grad=False, cache_labels=True, rank=0, world_size=1))
-    H.restated_train_one_epoch(m2, batches, loss, opt, H.make_scheduler(opt), args, _cpu_autocast)
-    assert loss.values == losses
-    for (k, a), (_, b) in zip(m.state_dict().items(), m2.state_dict().items()):
-        assert torch.equal(a, b), k
+    """The loop tests/test_trainer_gpu.py runs on the GPU box is the reference's, operation for operation: model.train,
+    scheduler, zero_grad, forward (on the same normalised images and tokens), loss, backward, clip_grad_norm_, step and clamp
+    in the same order under the same grad / autocast state as the reference's train_one_epoch driving the engine."""
+    trace = H.LoopTrace()
+    _run_loop(accum, nsteps, trace)
+    assert trace.events == [str(e) for e in TRACES[f"trace_a{accum}_n{nsteps}"]]

@@ -8,6 +8,8 @@ tests/test_trainer_cpu.py in the build container - and the expected numbers are 
 by the REAL trainer driving the REAL reference CLIP (oracle/make_train_golden.py): per-call loss (<= 2 %), clamped
 logit_scale, per-parameter update size, and the update direction of nine parameters (cosine >= 0.97).
 """
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -17,9 +19,11 @@ from oracle import clip_oracle as O
 from oracle import trainer_harness as H
 from oracle.make_golden import CASES
 
+from .conftest import GOLDEN
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-Z = np.load("tests/golden/train_loop_ref.npz")
+Z = np.load(os.path.join(GOLDEN, "train_loop_ref.npz"))
 
 
 def _autocast():
