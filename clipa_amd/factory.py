@@ -4,7 +4,8 @@ create_model (factory.py:121-259), create_loss (factory.py:262-290), create_mode
 
 Out of scope and rejected loudly: pretrained tags / HF hub download (network), timm / ResNet / CoCa /
 HF-text towers, torchscript.  The two image transforms create_model_and_transforms returns are
-clipa_amd.transform.image_transform (host-side, Pillow only).
+clipa_amd.transform.image_transform (host-side, Pillow only).  Distillation (--distill-model) is in scope: create_loss
+returns DistillClipLoss and the teacher is a second CLIP from create_model_and_transforms.
 """
 import logging
 from typing import Optional, Tuple, Union
@@ -12,7 +13,7 @@ from typing import Optional, Tuple, Union
 import torch
 
 from . import configs
-from .loss import ClipLoss
+from .loss import ClipLoss, DistillClipLoss
 from .model import (CLIP, OPENAI_DATASET_MEAN, OPENAI_DATASET_STD, convert_weights_to_lp, resize_pos_embed,
                     resize_text_pos_embed)
 
@@ -103,11 +104,12 @@ def create_model(
 
 
 def create_loss(args, model=None):
-    """factory.py:262-290 (plain ClipLoss branch).  `model` (optional, engine extension): bind the loss to the model so
-    that the image-feature all-gather starts under the text tower (ClipLoss.bind)."""
-    if getattr(args, "distill", False) or "coca" in getattr(args, "model", "").lower():
-        raise NotImplementedError("clipa_amd.create_loss: distillation / CoCa losses are out of scope")
-    loss = ClipLoss(
+    """factory.py:262-290 (ClipLoss and DistillClipLoss branches; CoCa is out of scope).  `model` (optional, engine
+    extension): bind the loss to the model so that the image-feature all-gather starts under the text tower (ClipLoss.bind)."""
+    if "coca" in getattr(args, "model", "").lower() and not getattr(args, "distill", False):
+        raise NotImplementedError("clipa_amd.create_loss: CoCa losses are out of scope")
+    cls = DistillClipLoss if getattr(args, "distill", False) else ClipLoss
+    loss = cls(
         local_loss=args.local_loss,
         gather_with_grad=args.gather_with_grad,
         cache_labels=True,

@@ -79,6 +79,9 @@ SIGNATURES = {
     "clipa_simce_workspace": (_I64, [_I64, _I64]),
     "clipa_simce_fwd": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _P, _P, _I64, _P]),
     "clipa_simce_bwd": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _F, _P, _P, _I64, _P, _P, _I64, _P]),
+    "clipa_simce_distill_workspace": (_I64, [_I64, _I64]),
+    "clipa_simce_distill_fwd": (_I32, [_P] * 4 + [_I64] * 8 + [_P, _P, _I64] + [_P] * 5 + [_I64, _P]),
+    "clipa_simce_distill_bwd": (_I32, [_P] * 4 + [_I64] * 8 + [_P, _P, _I64, _F] + [_P] * 5 + [_I64, _P, _P, _I64, _P]),
     "clipa_sum_scale": (_I32, [_P, _P, _I64, _F, _I32, _P]),
     "clipa_adamw": (_I32, [_P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _F, _F, _F, _I64, _F, _P]),
     "clipa_adamw_multi": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _F, _F, _F, _F, _F, _I64, _F, _P, _I32, _F, _F, _P]),

@@ -107,6 +107,50 @@ def _pad_rows8(x):
     return out
 
 
+def _wait_gathers(events):
+    """Make the compute stream wait for the side-stream gathers (timed for bench.py when wait_timing_start() is on)."""
+    cur = torch.cuda.current_stream()
+    if _WAITS is not None:
+        before = torch.cuda.Event(enable_timing=True)
+        before.record(cur)
+    for ev in events:
+        if ev is not None:
+            cur.wait_event(ev)
+    if _WAITS is not None:
+        after = torch.cuda.Event(enable_timing=True)
+        after.record(cur)
+        _WAITS.append((before, after))
+
+
+def _feature_grads(dli, dlt, i_rows, t_rows, i_all8, t_all8, B, E, N, local_loss, gather_with_grad, rank, W, group):
+    """d loss / d (local image, text features) [B, E] f32 from the bf16 d loss / d (I_rows T_all^T) and
+    d loss / d (T_rows I_all^T) (scale folded in): the four gradient GEMMs and the backward of the gather."""
+    # dli / dlt = d loss / d raw (the scale is already folded in).  raw_i = I_rows T_all^T ; raw_t = T_rows I_all^T
+    d_i_rows = ops.gemm_nt(dli, ops.transpose_bf16(t_all8), out_f32=True)              # [R, E]
+    d_t_rows = ops.gemm_nt(dlt, ops.transpose_bf16(i_all8), out_f32=True)
+    # d/d(gathered columns)
+    d_t_all = ops.gemm_tn(dli, i_rows, f32)[:N]                                        # [W*B, E]
+    d_i_all = ops.gemm_tn(dlt, t_rows, f32)[:N]
+    if W == 1:
+        d_i = d_i_rows + d_i_all
+        d_t = d_t_rows + d_t_all
+    elif local_loss:
+        d_i, d_t = d_i_rows, d_t_rows
+        if gather_with_grad:
+            rs = _reduce_scatter_fused(torch.cat([d_i_all, d_t_all], dim=1), W, group)
+            d_i = d_i + rs[:, :E]
+            d_t = d_t + rs[:, E:]
+    else:
+        # rows are the gathered features themselves: every term is a gradient w.r.t. the gather
+        full = torch.cat([d_i_rows + d_i_all, d_t_rows + d_t_all], dim=1)
+        if gather_with_grad:
+            rs = _reduce_scatter_fused(full, W, group)
+        else:
+            rs = full[rank * B:(rank + 1) * B]      # only the re-inserted local slice carries grad
+        d_i, d_t = rs[:, :E], rs[:, E:]
+    return d_i, d_t
+
+
 class ClipLossFn(torch.autograd.Function):
     """(CE(logits_per_image, y) + CE(logits_per_text, y)) / 2 with logits = s * I . T^T."""
 
@@ -123,17 +167,7 @@ class ClipLossFn(torch.autograd.Function):
                 ib = ops.to_bf16(img)
                 i_all, i_ev = _all_gather_bf16(ib, world_size, group)
             if img.is_cuda:
-                cur = torch.cuda.current_stream()
-                if _WAITS is not None:
-                    before = torch.cuda.Event(enable_timing=True)
-                    before.record(cur)
-                for ev in (i_ev, t_ev):
-                    if ev is not None:
-                        cur.wait_event(ev)
-                if _WAITS is not None:
-                    after = torch.cuda.Event(enable_timing=True)
-                    after.record(cur)
-                    _WAITS.append((before, after))
+                _wait_gathers((i_ev, t_ev))
         else:
             ib = ops.to_bf16(img)
             i_all, t_all = ib, tb
@@ -160,29 +194,8 @@ class ClipLossFn(torch.autograd.Function):
     def backward(ctx, dloss):
         dli, dlt, dsi, dst, i_rows, t_rows, i_all8, t_all8 = ctx.saved_tensors
         B, E, N, local_loss, gather_with_grad, rank, W, group, idt, tdt, sdt, sshape = ctx.meta
-        # dli / dlt = d loss / d raw (the scale is already folded in).  raw_i = I_rows T_all^T ; raw_t = T_rows I_all^T
-        d_i_rows = ops.gemm_nt(dli, ops.transpose_bf16(t_all8), out_f32=True)              # [R, E]
-        d_t_rows = ops.gemm_nt(dlt, ops.transpose_bf16(i_all8), out_f32=True)
-        # d/d(gathered columns)
-        d_t_all = ops.gemm_tn(dli, i_rows, f32)[:N]                                        # [W*B, E]
-        d_i_all = ops.gemm_tn(dlt, t_rows, f32)[:N]
-        if W == 1:
-            d_i = d_i_rows + d_i_all
-            d_t = d_t_rows + d_t_all
-        elif local_loss:
-            d_i, d_t = d_i_rows, d_t_rows
-            if gather_with_grad:
-                rs = _reduce_scatter_fused(torch.cat([d_i_all, d_t_all], dim=1), W, group)
-                d_i = d_i + rs[:, :E]
-                d_t = d_t + rs[:, E:]
-        else:
-            # rows are the gathered features themselves: every term is a gradient w.r.t. the gather
-            full = torch.cat([d_i_rows + d_i_all, d_t_rows + d_t_all], dim=1)
-            if gather_with_grad:
-                rs = _reduce_scatter_fused(full, W, group)
-            else:
-                rs = full[rank * B:(rank + 1) * B]      # only the re-inserted local slice carries grad
-            d_i, d_t = rs[:, :E], rs[:, E:]
+        d_i, d_t = _feature_grads(dli, dlt, i_rows, t_rows, i_all8, t_all8, B, E, N, local_loss, gather_with_grad, rank, W,
+                                  group)
         d_s = ops.sum_scale(dsi, 1.0)
         ops.sum_scale(dst, 1.0, out=d_s, accumulate=True)
         g = dloss.to(f32)
@@ -263,3 +276,99 @@ class ClipLoss(nn.Module):
             total_loss = ClipLossFn.apply(image_features.float(), text_features.float(), logit_scale, self.local_loss,
                                           self.gather_with_grad, self.rank, self.world_size, self.group, pend)
         return {"contrastive_loss": total_loss} if output_dict else total_loss
+
+
+class DistillClipLossFn(torch.autograd.Function):
+    """(contrastive, distill) of DistillClipLoss (loss.py:202-238) in one node, both directions: with student logits
+    z = s * I . T^T and teacher logits y = u * I_t . T_t^T, contrastive = mean over the two directions of CE(z, labels) and
+    distill = the same mean of -sum_j p_t(y)_j log p_s(z)_j (p: row distributions).  The teacher tensors are constants:
+    they get no gradient."""
+
+    @staticmethod
+    def forward(ctx, img, txt, logit_scale, d_img, d_txt, d_scale, local_loss, gather_with_grad, rank, world_size, group,
+                pend=None):
+        B, E = img.shape
+        Et = d_img.shape[1]
+        s_dev = logit_scale.detach().to(f32).reshape(1).contiguous().clone()     # read again by the backward kernels
+        u_dev = d_scale.detach().to(f32).reshape(1).contiguous().clone()
+        tb = ops.to_bf16(txt)
+        dib, dtb = ops.to_bf16(d_img.detach()), ops.to_bf16(d_txt.detach())
+        if world_size > 1:
+            # the teacher's features ride the student text gather: one [B, E + 2 E_t] byte all-gather instead of three
+            packed, p_ev = _all_gather_bf16(torch.cat([tb, dib, dtb], dim=1), world_size, group)
+            if pend is not None:
+                ib, i_all, i_ev = pend                                    # started before the text tower ran
+            else:
+                ib = ops.to_bf16(img)
+                i_all, i_ev = _all_gather_bf16(ib, world_size, group)
+            if img.is_cuda:
+                _wait_gathers((i_ev, p_ev))
+            t_all, di_all, dt_all = packed[:, :E].contiguous(), packed[:, E:E + Et], packed[:, E + Et:]
+        else:
+            ib = ops.to_bf16(img)
+            i_all, t_all, di_all, dt_all = ib, tb, dib, dtb
+        if world_size > 1 and not local_loss:
+            i_rows, t_rows, di_rows, dt_rows, label0 = i_all, t_all, di_all, dt_all, 0
+        else:
+            i_rows, t_rows, di_rows, dt_rows, label0 = ib, tb, dib, dtb, (B * rank if world_size > 1 else 0)
+        R, N = i_rows.shape[0], i_all.shape[0]
+        i_all8, t_all8 = _pad_rows8(i_all), _pad_rows8(t_all)
+        gs = 0.5 / R
+        # fused similarity GEMMs (student + teacher) + cross-entropy + distillation: no [R, N] logits reach HBM
+        ci, di, lsi, lti = ops.simce_distill(i_rows, t_all8, di_rows, dt_all, N, label0, s_dev, u_dev)
+        ct, dt, lst, ltt = ops.simce_distill(t_rows, i_all8, dt_rows, di_all, N, label0, s_dev, u_dev)
+        contrastive = ops.sum_scale(ci, gs)
+        ops.sum_scale(ct, gs, out=contrastive, accumulate=True)
+        distill = ops.sum_scale(di, gs)
+        ops.sum_scale(dt, gs, out=distill, accumulate=True)
+        if any(ctx.needs_input_grad[:3]):
+            ctx.save_for_backward(i_rows, t_rows, di_rows, dt_rows, i_all8, t_all8, di_all, dt_all, lsi, lti, lst, ltt, s_dev,
+                                  u_dev)
+            ctx.meta = (B, E, N, label0, local_loss, gather_with_grad, rank, world_size, group, img.dtype, txt.dtype,
+                        logit_scale.dtype, logit_scale.shape)
+        return contrastive, distill
+
+    @staticmethod
+    def backward(ctx, dcon, ddis):
+        i_rows, t_rows, di_rows, dt_rows, i_all8, t_all8, di_all, dt_all, lsi, lti, lst, ltt, s_dev, u_dev = ctx.saved_tensors
+        B, E, N, label0, local_loss, gather_with_grad, rank, W, group, idt, tdt, sdt, sshape = ctx.meta
+        gs = 0.5 / i_rows.shape[0]
+        # the upstream gradients stay on the device: the kernels fold them into the one bf16 d loss / d raw per direction
+        g_c = dcon.detach().to(f32).reshape(1).contiguous()
+        g_d = ddis.detach().to(f32).reshape(1).contiguous()
+        dli, dsi = ops.simce_distill_bwd(i_rows, t_all8, di_rows, dt_all, N, label0, gs, lsi, lti, s_dev, u_dev, g_c, g_d)
+        dlt, dst = ops.simce_distill_bwd(t_rows, i_all8, dt_rows, di_all, N, label0, gs, lst, ltt, s_dev, u_dev, g_c, g_d)
+        d_i, d_t = _feature_grads(dli, dlt, i_rows, t_rows, i_all8, t_all8, B, E, N, local_loss, gather_with_grad, rank, W,
+                                  group)
+        d_s = ops.sum_scale(dsi, 1.0)
+        ops.sum_scale(dst, 1.0, out=d_s, accumulate=True)
+        return (d_i.to(idt), d_t.to(tdt), d_s.to(sdt).reshape(sshape), None, None, None, None, None, None, None, None, None)
+
+
+class DistillClipLoss(ClipLoss):
+    """Same constructor / call contract as open_clip.loss.DistillClipLoss (loss.py:202-238):
+    `loss(image_features, text_features, logit_scale, dist_image_features, dist_text_features, dist_logit_scale,
+    output_dict=False)` -> {"contrastive_loss", "distill_loss"} or the 2-tuple.  The dist_* (teacher) tensors are constants,
+    as the reference trainer produces them under torch.no_grad() (train.py:206-209); one that requires grad is refused
+    instead of silently dropping its gradient.  Teacher and student embedding widths may differ."""
+
+    def forward(self, image_features, text_features, logit_scale, dist_image_features, dist_text_features, dist_logit_scale,
+                output_dict=False):
+        dev = image_features.device
+        if not torch.is_tensor(dist_logit_scale):
+            dist_logit_scale = torch.tensor(float(dist_logit_scale), device=dev)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in (dist_image_features, dist_text_features,
+                                                                      dist_logit_scale)):
+            raise RuntimeError("clipa_amd.DistillClipLoss: the dist_* (teacher) inputs require grad - the fused loss treats "
+                               "the teacher as a constant; compute them under torch.no_grad() or .detach() them")
+        pend = self._take_pending(image_features) if self.world_size > 1 else None
+        with torch.autocast(device_type=dev.type, enabled=False):
+            if not torch.is_tensor(logit_scale):
+                logit_scale = torch.tensor(float(logit_scale), device=dev)
+            contrastive, distill = DistillClipLossFn.apply(
+                image_features.float(), text_features.float(), logit_scale, dist_image_features.float(),
+                dist_text_features.float(), dist_logit_scale, self.local_loss, self.gather_with_grad, self.rank,
+                self.world_size, self.group, pend)
+        if output_dict:
+            return {"contrastive_loss": contrastive, "distill_loss": distill}
+        return contrastive, distill

@@ -971,6 +971,66 @@ def simce(rows, cols, n_valid, label0, gscale, scale=None, want_grad=True):
     return loss_rows, dl, dscale_rows
 
 
+def _distill_operands(rows_s, cols_s, rows_t, cols_t, n_valid, scale_s, scale_t, extra=()):
+    for t, name in ((rows_s, "rows_s"), (cols_s, "cols_s"), (rows_t, "rows_t"), (cols_t, "cols_t")):
+        _chk(t, bf16, name, 2)
+    rows_s, ldas = _rowmajor(rows_s)
+    cols_s, ldbs = _rowmajor(cols_s)
+    rows_t, ldat = _rowmajor(rows_t)
+    cols_t, ldbt = _rowmajor(cols_t)
+    R, Es = rows_s.shape
+    Et = rows_t.shape[1]
+    if rows_t.shape[0] != R:
+        raise RuntimeError(f"simce_distill: teacher rows {tuple(rows_t.shape)} vs student rows {tuple(rows_s.shape)}")
+    if cols_s.shape[1] != Es or cols_s.shape[0] < n_valid:
+        raise RuntimeError(f"simce_distill: cols_s {tuple(cols_s.shape)} does not cover {n_valid} x {Es}")
+    if cols_t.shape[1] != Et or cols_t.shape[0] < n_valid:
+        raise RuntimeError(f"simce_distill: cols_t {tuple(cols_t.shape)} does not cover {n_valid} x {Et}")
+    for t, name in ((scale_s, "scale_s"), (scale_t, "scale_t")) + tuple(extra):
+        if t is not None:
+            _chk(t, f32, name)
+    return (rows_s, cols_s, rows_t, cols_t), (R, Es, Et, ldas, ldbs, ldat, ldbt)
+
+
+def simce_distill(rows_s, cols_s, rows_t, cols_t, n_valid, label0, scale_s=None, scale_t=None):
+    """Forward of the fused similarity + cross-entropy + distillation loss (one direction of DistillClipLoss): student
+    logits z = s * rows_s @ cols_s[:n_valid]^T, teacher logits y = u * rows_t @ cols_t[:n_valid]^T, labels label0 + row.
+    rows_* [R, E_*], cols_* [>= n_valid, E_*] bf16 (E_s and E_t may differ); s, u f32 DEVICE scalars (None = 1).
+    Returns f32 [R] ce_rows = lse(z) - z[label], dist_rows = -sum softmax(y) log_softmax(z), lse_s and lse_t (the last
+    two feed simce_distill_bwd).  Neither logit matrix exists in HBM."""
+    ops4, (R, Es, Et, ldas, ldbs, ldat, ldbt) = _distill_operands(rows_s, cols_s, rows_t, cols_t, n_valid, scale_s, scale_t)
+    dev = ops4[0].device
+    wsb = lib.query("clipa_simce_distill_workspace", R, n_valid)
+    ws = torch.empty(max(wsb, 4) // 4, device=dev, dtype=f32)
+    lse_s, lse_t, ce_rows, dist_rows = (torch.empty(R, device=dev, dtype=f32) for _ in range(4))
+    with _Timed("simce_distill", 2.0 * R * n_valid * (Es + Et)):
+        lib.call("clipa_simce_distill_fwd", *(_p(t) for t in ops4), R, n_valid, Es, Et, ldas, ldbs, ldat, ldbt, _p(scale_s),
+                 _p(scale_t), label0, _p(lse_s), _p(lse_t), _p(ce_rows), _p(dist_rows), _p(ws), wsb, _stream())
+    return ce_rows, dist_rows, lse_s, lse_t
+
+
+def simce_distill_bwd(rows_s, cols_s, rows_t, cols_t, n_valid, label0, gscale, lse_s, lse_t, scale_s=None, scale_t=None,
+                      g_c=None, g_d=None):
+    """Backward of simce_distill: re-runs both similarity GEMMs and returns the bf16
+    d loss / d (rows_s @ cols_s^T) = s * gscale * (g_c (p^s - onehot) + g_d (p^s - p^t))  [R, n8] (n8 = n_valid rounded
+    up to 8, pad columns zero) and the per-row d loss / d s f32 [R].  g_c, g_d: upstream gradients of the two losses as
+    f32 DEVICE scalars (None = 1) - no host sync.  The teacher gets no gradient."""
+    ops4, (R, Es, Et, ldas, ldbs, ldat, ldbt) = _distill_operands(rows_s, cols_s, rows_t, cols_t, n_valid, scale_s, scale_t,
+                                                                  ((lse_s, "lse_s"), (lse_t, "lse_t"), (g_c, "g_c"),
+                                                                   (g_d, "g_d")))
+    dev = ops4[0].device
+    n8 = (n_valid + 7) // 8 * 8
+    wsb = lib.query("clipa_simce_distill_workspace", R, n_valid)
+    ws = torch.empty(max(wsb, 4) // 4, device=dev, dtype=f32)
+    dl = torch.empty((R, n8), device=dev, dtype=bf16)
+    dscale_rows = torch.empty(R, device=dev, dtype=f32)
+    with _Timed("simce_distill_bwd", 2.0 * R * n_valid * (Es + Et)):
+        lib.call("clipa_simce_distill_bwd", *(_p(t) for t in ops4), R, n_valid, Es, Et, ldas, ldbs, ldat, ldbt, _p(scale_s),
+                 _p(scale_t), label0, float(gscale), _p(g_c), _p(g_d), _p(lse_s.contiguous()), _p(lse_t.contiguous()),
+                 _p(dl), n8, _p(dscale_rows), _p(ws), wsb, _stream())
+    return dl, dscale_rows
+
+
 def sum_scale(x, scale, out=None, accumulate=False):
     x = x.contiguous()
     if out is None:

@@ -280,6 +280,23 @@ int clipa_simce_fwd(const void* rows, const void* cols, int64_t R, int64_t N, in
 int clipa_simce_bwd(const void* rows, const void* cols, int64_t R, int64_t N, int64_t E, int64_t lda, int64_t ldb,
                     const float* scale, int64_t label0, float gscale, const float* lse, void* dlogits_bf16,
                     int64_t ldd, float* dscale_rows, void* workspace, int64_t workspace_bytes, void* stream);
+/* Fused similarity + cross-entropy + distillation loss of DistillClipLoss (loss.py:202-238), one direction: student
+ * logits z = s * rows_s . cols_s^T ([R,E_s] . [N,E_s]^T), teacher logits y = u * rows_t . cols_t^T ([R,E_t] . [N,E_t]^T),
+ * bf16 operands, s and u read from DEVICE memory (NULL = 1), labels label0 + r.  Forward: lse_s[R], lse_t[R],
+ * ce_rows[R] = lse_s - z[label], dist_rows[R] = lse_s - sum_j softmax(y)_j z_j; neither logit matrix is written.
+ * Backward: the bf16 d loss / d (rows_s . cols_s^T) = s * gscale * (g_c (p^s - onehot) + g_d (p^s - p^t)) ([R, ldd],
+ * ldd >= N rounded up to 8, pad columns zero) plus dscale_rows[R] = per-row d loss / d s; g_c, g_d are DEVICE scalars
+ * (NULL = 1), the teacher gets no gradient.  Workspace: clipa_simce_distill_workspace(R, N) bytes for either call. */
+int64_t clipa_simce_distill_workspace(int64_t R, int64_t N);
+int clipa_simce_distill_fwd(const void* rows_s, const void* cols_s, const void* rows_t, const void* cols_t, int64_t R,
+                            int64_t N, int64_t Es, int64_t Et, int64_t ldas, int64_t ldbs, int64_t ldat, int64_t ldbt,
+                            const float* scale_s, const float* scale_t, int64_t label0, float* lse_s, float* lse_t,
+                            float* ce_rows, float* dist_rows, void* workspace, int64_t workspace_bytes, void* stream);
+int clipa_simce_distill_bwd(const void* rows_s, const void* cols_s, const void* rows_t, const void* cols_t, int64_t R,
+                            int64_t N, int64_t Es, int64_t Et, int64_t ldas, int64_t ldbs, int64_t ldat, int64_t ldbt,
+                            const float* scale_s, const float* scale_t, int64_t label0, float gscale, const float* g_c,
+                            const float* g_d, const float* lse_s, const float* lse_t, void* dlogits_bf16, int64_t ldd,
+                            float* dscale_rows, void* workspace, int64_t workspace_bytes, void* stream);
 int clipa_sum_scale(const float* in, float* out, int64_t n, float scale, int accumulate, void* stream);
 
 /* AdamW over one flat tensor (training/main.py:318-326 torch.optim.AdamW + train.py:285-286 clamp is
