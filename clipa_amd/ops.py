@@ -1031,6 +1031,45 @@ def simce_distill_bwd(rows_s, cols_s, rows_t, cols_t, n_valid, label0, gscale, l
     return dl, dscale_rows
 
 
+def retrieval_ranks(img, txt, scale=None):
+    """Retrieval ranks of the positives of get_clip_metrics (train.py:432-449) without the [N, N] logits: img, txt
+    f32 [N, E] (row i of each a matched pair), v = s * img @ txt^T in fp32 with s = scale[0] read on the device (None = 1).
+    Returns int32 [N] (i2t_gt, i2t_eq, t2i_gt, t2i_eq): per image row i the number of other texts j with v_ij > v_ii /
+    v_ij == v_ii, per text column j the number of other images i with v_ij > v_jj / == v_jj.  The reference's 0-based
+    rank from an unstable argsort lies in [gt, gt + eq]; gt (ties broken in the positive's favour) is the engine's rank."""
+    _chk(img, f32, "img", 2)
+    _chk(txt, f32, "txt", 2)
+    if img.shape != txt.shape:
+        raise RuntimeError(f"retrieval_ranks: img {tuple(img.shape)} and txt {tuple(txt.shape)} must be the same [N, E]")
+    img, lda = _rowmajor(img)
+    txt, ldb = _rowmajor(txt)
+    if lda % 4 or img.data_ptr() % 16:
+        img, lda = _pad_cols4(img)
+    if ldb % 4 or txt.data_ptr() % 16:
+        txt, ldb = _pad_cols4(txt)
+    N, E = img.shape
+    if scale is not None:
+        _chk(scale, f32, "scale")
+        scale = scale.reshape(1).contiguous()
+    dev = img.device
+    wsb = lib.query("clipa_retrieval_ranks_workspace", N)
+    ws = torch.empty(max(wsb, 16) // 4, device=dev, dtype=f32)
+    out = torch.empty((4, (N + 3) // 4 * 4), device=dev, dtype=torch.int32)       # rows 16-byte aligned
+    with _Timed("retrieval_ranks", 2.0 * N * N * E):
+        lib.call("clipa_retrieval_ranks", _p(img), _p(txt), N, E, lda, ldb, _p(scale), *(_p(out[k]) for k in range(4)), _p(ws),
+                 wsb, _stream())
+    return tuple(out[k, :N] for k in range(4))
+
+
+def _pad_cols4(x):
+    """[N, E] -> (a [N, E] view of a fresh [N, E rounded up to 4] buffer, its row stride): the kernel wants 16-byte
+    aligned rows."""
+    n, e = x.shape
+    buf = torch.empty((n, (e + 3) // 4 * 4), device=x.device, dtype=x.dtype)
+    buf[:, :e] = x
+    return buf[:, :e], buf.shape[1]
+
+
 def sum_scale(x, scale, out=None, accumulate=False):
     x = x.contiguous()
     if out is None:

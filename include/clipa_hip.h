@@ -298,6 +298,19 @@ int clipa_simce_distill_bwd(const void* rows_s, const void* cols_s, const void* 
                             const float* g_d, const float* lse_s, const float* lse_t, void* dlogits_bf16, int64_t ldd,
                             float* dscale_rows, void* workspace, int64_t workspace_bytes, void* stream);
 int clipa_sum_scale(const float* in, float* out, int64_t n, float scale, int accumulate, void* stream);
+/* Retrieval ranks of the validation metrics (get_clip_metrics, clipa_torch/training/train.py:432-449) without the [N, N]
+ * logit matrix.  A (image features) and B (text features) are fp32 [N, E] with leading dimensions lda, ldb (>= E, multiples
+ * of 4), row i of each a matched pair; s is read from DEVICE memory (NULL = 1).  With v_ij = fl(s * (A_i . B_j)), every x_ij
+ * computed by the same fp32 arithmetic (one ascending-k fmaf chain per output, the diagonal included):
+ *   i2t_gt[i] = #{j != i : v_ij > v_ii}   i2t_eq[i] = #{j != i : v_ij == v_ii}   (row i, image -> text)
+ *   t2i_gt[j] = #{i != j : v_ij > v_jj}   t2i_eq[j] = #{i != j : v_ij == v_jj}   (column j, text -> image)
+ * Tie rule: the reference's 0-based position of the positive after an unstable descending argsort is some value in
+ * [gt, gt + eq]; gt is the optimistic, deterministic choice the engine reports.  All pointers 16-byte aligned (scale 4);
+ * the count arrays need no clearing.  Workspace: clipa_retrieval_ranks_workspace(N) bytes.  Memory is O(N). */
+int64_t clipa_retrieval_ranks_workspace(int64_t N);
+int clipa_retrieval_ranks(const float* A, const float* B, int64_t N, int64_t E, int64_t lda, int64_t ldb,
+                          const float* scale, int32_t* i2t_gt, int32_t* i2t_eq, int32_t* t2i_gt, int32_t* t2i_eq,
+                          void* workspace, int64_t workspace_bytes, void* stream);
 
 /* AdamW over one flat tensor (training/main.py:318-326 torch.optim.AdamW + train.py:285-286 clamp is
  * done by the caller): p -= lr*(m_hat/(sqrt(v_hat)+eps) + wd*p). param/grad bf16 or f32; m, v f32. */
