@@ -14,6 +14,8 @@ Activation policy: a block keeps only its bf16 input and recomputes the rest in 
 reference does with --grad-checkpointing, transformer.py:320-325), so ViT-L/16 at local batch 4096
 (806 912 tokens) fits in HBM with whole-batch GEMMs (M = 806 912) instead of micro-batches.
 """
+import collections
+import dataclasses
 import weakref
 
 import torch
@@ -21,7 +23,6 @@ import torch
 from . import ops
 
 bf16, f32 = torch.bfloat16, torch.float32
-
 
 
 class WeightCache:
@@ -65,63 +66,66 @@ def _like_param(g, p):
 
 
 # ---------------------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class BlockCfg:
+    """A residual block's settings, built by model.Transformer.run.  keep: what the block stores for its backward besides its
+    input - "qkv", "a" (attention output + softmax statistics), "x1", "h" (bf16 MLP pre-activation) or "h8" (the same as saturating
+    e4m3 bytes written by the c_fc epilogue); the bf16 backward-time recompute adds "h1", "h2", "g" (LayerNorm outputs and the
+    activation, _KEEP_ALL).  fp8 blocks: grad_fmt = ops.FMT_* of the gradient operands, predict = the fp8_predicted_scales knob,
+    handoff = the tower's GradHandoff; offer: the LayerNorm-1 backward hands dx to the block in front (not a tower's first)."""
+    B: int
+    L: int
+    H: int
+    causal: bool
+    act: int
+    eps: float
+    varlen: object
+    fp8: bool
+    grad_fmt: int
+    predict: bool
+    keep: frozenset
+    handoff: object
+    offer: bool
+
+
+_KEEP_ALL = frozenset(("h1", "qkv", "a", "x1", "h2", "h", "g"))
+
+
 def _attn_fwd(qkv, cfg, want_stats):
     """-> (attention output, softmax statistics | None); fixed-length batches or packed variable-length sequences."""
-    vl = cfg.get("varlen")
-    if vl is not None:
-        r = ops.attention_fwd_varlen(qkv, vl, cfg["H"], cfg["causal"], want_stats=want_stats)
+    if cfg.varlen is not None:
+        r = ops.attention_fwd_varlen(qkv, cfg.varlen, cfg.H, cfg.causal, want_stats=want_stats)
     else:
-        r = ops.attention_fwd(qkv, cfg["B"], cfg["L"], cfg["H"], cfg["causal"], want_stats=want_stats)
+        r = ops.attention_fwd(qkv, cfg.B, cfg.L, cfg.H, cfg.causal, want_stats=want_stats)
     return r if want_stats else (r, None)
 
 
 def _attn_bwd(qkv, a, da, stats, cfg):
-    vl = cfg.get("varlen")
-    if vl is not None:
-        return ops.attention_bwd_varlen(qkv, a, da, stats, vl, cfg["H"], cfg["causal"])
-    return ops.attention_bwd(qkv, a, da, stats, cfg["B"], cfg["L"], cfg["H"], cfg["causal"])
+    if cfg.varlen is not None:
+        return ops.attention_bwd_varlen(qkv, a, da, stats, cfg.varlen, cfg.H, cfg.causal)
+    return ops.attention_bwd(qkv, a, da, stats, cfg.B, cfg.L, cfg.H, cfg.causal)
 
 
 def _block_forward(x, P, cfg, keep, need_y=True):
-    """x [M,D] bf16. P: dict of operand tensors. Returns y and (if keep) the intermediates.
-    keep: False (nothing), True / "full" (everything the backward reads), "light" (only the GEMM / attention
-    outputs qkv, a, stats, x1, hpre - LayerNorm outputs and the activation are re-materialised in backward),
-    "light8" (light with hpre kept as saturating e4m3 bytes written by the c_fc epilogue itself: 14 instead of 18 bytes
-    per element of x; the backward takes gelu'(h) and the re-materialised activation from the e4m3 value - ~3 % rms
-    rounding of h, the only tier whose gradients are not bit-identical to the recomputed block's) or
-    "medium" (light without hpre, 10 bytes per element of x: backward re-runs LN2 + the c_fc GEMM,
-    a third of the block's forward FLOPs, and skips the other three GEMMs and attention)."""
-    B, L, H, causal, act = cfg["B"], cfg["L"], cfg["H"], cfg["causal"], cfg["act"]
-    if cfg.get("fp8"):
-        return _block_forward_fp8(x, P, cfg, keep, need_y)[:2]
-    # the named tiers are sets of kept tensors; a frozenset names them one by one (round 4: what a byte buys differs per tensor -
-    # the e4m3 pre-activation ~1.5 ms per GB, the attention output ~0.94, x1 ~0.91, qkv ~0.79 at ViT-L/16 - so bench.py's planner
-    # keeps them independently): "qkv", "a" (with the softmax statistics), "x1", "h" (bf16 pre-activation) or "h8" (e4m3)
-    ks = KEEP_SETS.get(keep, keep) if keep and keep is not True and keep != "full" else None
-    full = bool(keep) and ks is None
-    h1 = ops.layernorm_fwd(x, P["ln1_w"], P["ln1_b"], cfg["eps"])
+    """x [M,D] bf16. P: dict of operand tensors. keep: BlockCfg.keep, or _KEEP_ALL.  Returns y and (if keep) the
+    intermediates (h1, qkv, a, stats, x1, h2, hpre, g), None where not kept: the backward re-materialises them."""
+    h1 = ops.layernorm_fwd(x, P["ln1_w"], P["ln1_b"], cfg.eps)
     qkv = ops.gemm_nt(h1, P["w_in"], P["b_in"])
-    a, stats = _attn_fwd(qkv, cfg, full or (ks is not None and "a" in ks))
+    a, stats = _attn_fwd(qkv, cfg, "a" in keep)
     x1 = ops.gemm_nt(a, P["w_out"], P["b_out"], epi=ops.EPI_ADD, aux=x)
-    h2 = ops.layernorm_fwd(x1, P["ln2_w"], P["ln2_b"], cfg["eps"])
-    want_pre = "e4m3" if (ks is not None and "h8" in ks) else (full or (ks is not None and "h" in ks))
+    h2 = ops.layernorm_fwd(x1, P["ln2_w"], P["ln2_b"], cfg.eps)
+    want_pre = "e4m3" if "h8" in keep else "h" in keep
     if want_pre:
-        g, hpre = ops.gemm_nt(h2, P["w_fc"], P["b_fc"], epi=ops.EPI_ACT, act=act, want_pre=want_pre)
+        g, hpre = ops.gemm_nt(h2, P["w_fc"], P["b_fc"], epi=ops.EPI_ACT, act=cfg.act, want_pre=want_pre)
     else:
-        g, hpre = ops.gemm_nt(h2, P["w_fc"], P["b_fc"], epi=ops.EPI_ACT, act=act), None
+        g, hpre = ops.gemm_nt(h2, P["w_fc"], P["b_fc"], epi=ops.EPI_ACT, act=cfg.act), None
     # (need_y=False: the backward-time recompute of a block wants the intermediates only - its output is the next block's input,
     # which that block kept; the c_proj GEMM would be thrown away)
     y = ops.gemm_nt(g, P["w_proj"], P["b_proj"], epi=ops.EPI_ADD, aux=x1) if need_y else None
-    if full:
-        return y, (h1, qkv, a, stats, x1, h2, hpre, g)
-    if ks:
-        return y, (None, qkv if "qkv" in ks else None, a if "a" in ks else None, stats if "a" in ks else None,
-                   x1 if "x1" in ks else None, None, hpre, None)
-    return y, None
-
-
-KEEP_SETS = {"light": frozenset(("qkv", "a", "x1", "h")), "light8": frozenset(("qkv", "a", "x1", "h8")),
-             "medium": frozenset(("qkv", "a", "x1"))}
+    if not keep:
+        return y, None
+    return y, (h1 if "h1" in keep else None, qkv if "qkv" in keep else None, a if "a" in keep else None, stats,
+               x1 if "x1" in keep else None, h2 if "h2" in keep else None, hpre, g if "g" in keep else None)
 
 
 def _lin8(xq, xs, P, name, **kw):
@@ -133,13 +137,13 @@ def _lin8(xq, xs, P, name, **kw):
 def _gradq8(dy, cfg):
     """The incoming gradient of a linear layer as fp8 operand, quantised ONCE per token for both of its products (input gradient
     and weight gradient), and its column sums = the layer's bias gradient from the same pass: -> (dq, ds, colsum)."""
-    return ops.quantize_rows(dy, cfg.get("fp8_grad_fmt", ops.FMT_E4M3), want_colsum=True)
+    return ops.quantize_rows(dy, cfg.grad_fmt, want_colsum=True)
 
 
 def _dlin8(dq, ds, P, name, cfg, **kw):
     """fp8 input gradient: the per-token quantised gradient against the cached quantised W^T."""
     wq, ws = P["wt8_" + name]
-    return ops.gemm_nt_f8(dq, ds, wq, ws, None, fmt_a=cfg.get("fp8_grad_fmt", ops.FMT_E4M3), **kw)
+    return ops.gemm_nt_f8(dq, ds, wq, ws, None, fmt_a=cfg.grad_fmt, **kw)
 
 
 def _wgrad8(dq, ds, sx, emit, out_dtype, cfg):
@@ -148,68 +152,48 @@ def _wgrad8(dq, ds, sx, emit, out_dtype, cfg):
     with one device scalar t = max_m ds[m] sx[m] (sx = the activation's own row scale of the forward pass: nothing saturates, no
     amax history, recompute reproduces the bytes) and dW = t * dq^T X8.  emit(ds, t) -> X8 (the kernel that has X at hand)."""
     t = ops.rowscale_max(ds, sx)
-    return ops.gemm_tn_f8(dq, emit(ds, t), t=t, fmt_p=cfg.get("fp8_grad_fmt", ops.FMT_E4M3), out_dtype=out_dtype)
+    return ops.gemm_tn_f8(dq, emit(ds, t), t=t, fmt_p=cfg.grad_fmt, out_dtype=out_dtype)
 
 
-def _fp8_keep_set(keep):
-    """-> (kept tensor names | None, full): the named tiers of the bf16 engine and its per-tensor sets ("qkv", "a" = attention output +
-    statistics, "x1", "h" = bf16 pre-activation, "h8" = the same as saturating e4m3 bytes written by the c_fc epilogue) hold in fp8
-    mode too (round 6); True / "full" additionally keeps the LayerNorm outputs and the activation in bf16."""
-    if not keep:
-        return None, False
-    if keep is True or keep == "full":
-        return KEEP_SETS["light"], True
-    return KEEP_SETS.get(keep, keep), False
-
-
-def _block_forward_fp8(x, P, cfg, keep, need_y=True, scales=None):
+def _block_forward_fp8(x, P, cfg, keep):
     """_block_forward with the four linear layers on the fp8 MFMA path (BASELINE.json configs[3]): the LayerNorms emit the
     e4m3 operand of the GEMM that follows them, the attention output and the MLP activation are quantised per token by
     clipa_quantize_rows; everything between the GEMMs (residual stream, attention, softmax statistics, kept tensors) is
-    bf16 exactly as in the bf16 engine.  -> (y, kept tensors | None, scales): scales = the per-token scales (s1, sa, s2, sg) of
-    the four GEMM inputs (LN1 output, attention output, LN2 output, activation), a few MB that every block keeps - the fp8
-    weight gradients of the backward derive their tensor scale from them (_wgrad8).  need_y=False: no output, only what the
-    backward reads (_fp8_fill on nothing)."""
-    B, L, H, causal, act = cfg["B"], cfg["L"], cfg["H"], cfg["causal"], cfg["act"]
-    if not need_y:
-        return None, _fp8_fill(x, (None,) * 8, P, cfg), scales
-    ks, full = _fp8_keep_set(keep)
-    ks = ks or frozenset()
-    h1, q1, s1 = ops.layernorm_fwd_q8(x, P["ln1_w"], P["ln1_b"], cfg["eps"], want_bf16=full)
+    bf16 exactly as in the bf16 engine.  keep: the names of BlockCfg.keep; the LayerNorm outputs and the activation are never
+    kept (the fp8 backward re-materialises them as e4m3 operands).  -> (y, kept (qkv, a, stats, x1, hpre) | None, scales):
+    scales = the per-token scales (s1, sa, s2, sg) of the four GEMM inputs (LN1 output, attention output, LN2 output,
+    activation), a few MB that every block keeps - the fp8 weight gradients of the backward derive their tensor scale from
+    them (_wgrad8)."""
+    _, q1, s1 = ops.layernorm_fwd_q8(x, P["ln1_w"], P["ln1_b"], cfg.eps)
     qkv = _lin8(q1, s1, P, "in")
     del q1
-    a, stats = _attn_fwd(qkv, cfg, "a" in ks)
+    a, stats = _attn_fwd(qkv, cfg, "a" in keep)
     qa, sa = ops.quantize_rows(a)
     x1 = _lin8(qa, sa, P, "out", epi=ops.EPI_ADD, aux=x)
     del qa
-    h2, q2, s2, rn2 = ops.layernorm_fwd_q8(x1, P["ln2_w"], P["ln2_b"], cfg["eps"], want_bf16=full, want_rownorm=True)      # (the row norms: 4 bytes per row)
-    want_pre = "e4m3" if "h8" in ks else ("h" in ks or full)
+    want_pre = "e4m3" if "h8" in keep else "h" in keep
     # Engine knob `fp8_predicted_scales` (round 6, off by default): the activation leaves the c_fc GEMM as the e4m3 operand of
     # c_proj (no bf16 copy, no row quantiser pass).  A tile of the GEMM cannot know its row's maximum, so the row scale is PREDICTED: |h[m,c]| <= ||LN2(x1)[m,:]|| * max_c ||W_fc[c,:]|| +
     # max |b_fc| (Cauchy-Schwarz; 1.13 covers the e4m3 rounding of both operands) and |gelu(h)| <= |h| - a rigorous bound, a few
     # binades above the row's true maximum, well inside e4m3's range.  Every tier uses the same scales (bit-identical forwards);
-    # ragged shapes / the all-stored mode run GEMM + scaled quantiser with the same arithmetic.  Price (tests/test_fp8_gpu.py,
+    # ragged shapes run GEMM + scaled quantiser with the same arithmetic.  Price (tests/test_fp8_gpu.py,
     # DESIGN 4): per-tensor gradient cosines against the fp32 reference 0.001-0.009 lower than with the rows' true maxima.
-    sg, so = ops.row_bound(rn2, P["wn_fc"], P["bmax_fc"], 1.13) if cfg.get("fp8_predict") else (None, None)
-    if not cfg.get("fp8_predict"):      # the default: bf16 activation + a row quantiser with the row's TRUE maximum
-        r = _lin8(q2, s2, P, "fc", epi=ops.EPI_ACT, act=act, want_pre=want_pre)
+    if cfg.predict:
+        _, q2, s2, rn2 = ops.layernorm_fwd_q8(x1, P["ln2_w"], P["ln2_b"], cfg.eps, want_rownorm=True)    # (4 bytes per row)
+        sg, so = ops.row_bound(rn2, P["wn_fc"], P["bmax_fc"], 1.13)
+        r = _lin8(q2, s2, P, "fc", epi=ops.EPI_ACT, act=cfg.act, want_pre=want_pre, out_scale=so)
+        qg, hpre = r if want_pre else (r, None)
+    else:      # the default: bf16 activation + a row quantiser with the row's TRUE maximum
+        _, q2, s2 = ops.layernorm_fwd_q8(x1, P["ln2_w"], P["ln2_b"], cfg.eps)
+        r = _lin8(q2, s2, P, "fc", epi=ops.EPI_ACT, act=cfg.act, want_pre=want_pre)
         g, hpre = r if want_pre else (r, None)
         qg, sg = ops.quantize_rows(g)
-        g = g if full else None
-    elif full:
-        g, hpre = _lin8(q2, s2, P, "fc", epi=ops.EPI_ACT, act=act, want_pre=True)
-        qg = ops.scale_quantize_rows(g, so, P["one"])
-    else:
-        r = _lin8(q2, s2, P, "fc", epi=ops.EPI_ACT, act=act, want_pre=want_pre, out_scale=so)
-        (qg, hpre), g = (r if want_pre else (r, None)), None
+        del g
     del q2
     y = _lin8(qg, sg, P, "proj", epi=ops.EPI_ADD, aux=x1)
     del qg
-    sc = (s1, sa, s2, sg)
-    if not ks:
-        return y, None, sc
-    return y, (h1 if full else None, qkv if "qkv" in ks else None, a if "a" in ks else None, stats if "a" in ks else None,
-               x1 if "x1" in ks else None, h2 if full else None, hpre, g if full else None), sc
+    kept = (qkv if "qkv" in keep else None, a if "a" in keep else None, stats, x1 if "x1" in keep else None, hpre)
+    return y, kept if keep else None, (s1, sa, s2, sg)
 
 
 def _fp8_fill(x, kept, P, cfg):
@@ -217,9 +201,9 @@ def _fp8_fill(x, kept, P, cfg):
     as the forward produced it.  The activation itself is never rebuilt in bf16: the weight gradient of c_proj re-materialises
     it as an fp8 operand from the pre-activation (_block_backward_fp8), so a missing pre-activation costs LN2 + the c_fc GEMM
     with a plain epilogue."""
-    h1, qkv, a, stats, x1, h2, hpre, g = kept
+    qkv, a, stats, x1, hpre = kept or (None,) * 5
     if qkv is None:
-        _, q1, s1 = ops.layernorm_fwd_q8(x, P["ln1_w"], P["ln1_b"], cfg["eps"], want_bf16=False)
+        _, q1, s1 = ops.layernorm_fwd_q8(x, P["ln1_w"], P["ln1_b"], cfg.eps)
         qkv = _lin8(q1, s1, P, "in")
         del q1
     if a is None:
@@ -229,56 +213,56 @@ def _fp8_fill(x, kept, P, cfg):
         x1 = _lin8(qa, sa, P, "out", epi=ops.EPI_ADD, aux=x)
         del qa
     if hpre is None:
-        _, q2, s2 = ops.layernorm_fwd_q8(x1, P["ln2_w"], P["ln2_b"], cfg["eps"], want_bf16=False)
+        _, q2, s2 = ops.layernorm_fwd_q8(x1, P["ln2_w"], P["ln2_b"], cfg.eps)
         hpre = _lin8(q2, s2, P, "fc")          # bf16(LN2(x1) W^T + b): what the activation epilogue's second output holds
         del q2
-    return (h1, qkv, a, stats, x1, h2, hpre, g)
+    return (qkv, a, stats, x1, hpre)
 
 
-# The LayerNorm-1 backward of block i writes dx = the gradient block i-1 receives - and, in fp8 mode, that gradient's row-quantised
-# form with its column sums (ops.layernorm_bwd(q8_fmt=...)): block i-1's backward starts from exactly that (its c_proj products
-# and bias gradient).  The autograd edge between two ResBlockFn nodes carries one tensor, so the operand travels beside it: one
-# slot, taken (and cleared) by the next fp8 block backward that runs.  The slot holds dx itself, so its memory cannot be
-# recycled while the offer stands: a gradient that arrives with dx's address, shape and version IS dx (a summed or copied
-# gradient is another allocation and is quantised the ordinary way).
-_Q8_HANDOFF = []
+class GradHandoff:
+    """The LayerNorm-1 backward of block i writes dx = the gradient block i-1 receives - and, in fp8 mode, that gradient's
+    row-quantised form with its column sums (ops.layernorm_bwd(q8_fmt=...)): block i-1's backward starts from exactly that (its
+    c_proj products and bias gradient).  The autograd edge between two ResBlockFn nodes carries one tensor, so the operand
+    travels beside it: one slot per tower, taken (and cleared) by the next fp8 block backward of that tower.  The slot holds dx
+    itself, so its memory cannot be recycled while the offer stands: a gradient that arrives with dx's address, shape and version
+    IS dx (a summed or copied gradient is another allocation and is quantised the ordinary way)."""
+
+    def __init__(self):
+        self._slot = None
+
+    def offer(self, dx, q8, fmt):
+        self._slot = (dx, dx._version, fmt, q8)
+
+    def take(self, dy, fmt):
+        slot, self._slot = self._slot, None
+        if slot is not None:
+            dx, version, f, q8 = slot
+            if f == fmt and dy.data_ptr() == dx.data_ptr() and dy.shape == dx.shape and dy.stride() == dx.stride() \
+                    and dy.dtype == dx.dtype and dy._version == version:      # (the version at the offer: an in-place hook would move it)
+                return q8
+        return None
+
+    def clear(self):
+        self._slot = None
 
 
-def _q8_offer(dx, q8, fmt):
-    _Q8_HANDOFF[:] = [(dx, dx._version, fmt, q8)]
-
-
-def _q8_take(dy, fmt):
-    slot = _Q8_HANDOFF[:]
-    del _Q8_HANDOFF[:]
-    if slot:
-        dx, version, f, q8 = slot[0]
-        if f == fmt and dy.data_ptr() == dx.data_ptr() and dy.shape == dx.shape and dy.stride() == dx.stride() \
-                and dy.dtype == dx.dtype and dy._version == version:      # (the version at the offer: an in-place hook would move it)
-            return q8
-    return None
-
-
-def _block_backward_fp8(x, dy, box, P, cfg, scales):
+def _block_backward_fp8(x, dy, box, P, cfg, scales, offer):
     """Backward of a block in fp8 mode: every matrix product - input gradients AND (round 6) weight gradients - on
     v_mfma_f32_16x16x128_f8f6f4.  Each incoming gradient is quantised once per token (its column sums = the bias gradient ride
     the same pass) and feeds both products of its layer; the activation operand of a weight gradient is emitted as e4m3 by the
-    kernel that re-materialises it anyway (LayerNorm, GELU) with the gradient's token scale folded in (_wgrad8)."""
-    act, eps = cfg["act"], cfg["eps"]
-    h1, qkv, a, stats, x1, h2, hpre, g = box.pop()
+    kernel that re-materialises it anyway (LayerNorm, GELU) with the gradient's token scale folded in (_wgrad8).  offer: hand dx
+    and its fp8 form to the block in front of this one (cfg.handoff)."""
+    act, eps, fmt = cfg.act, cfg.eps, cfg.grad_fmt
+    qkv, a, stats, x1, hpre = box.pop()
     s1, sa, s2, sg = scales
     dy = dy.contiguous()
-    fmt = cfg.get("fp8_grad_fmt", ops.FMT_E4M3)
-    # y = x1 + c_proj(gelu(hpre))
-    dq, ds, d_b_proj, rn = _q8_take(dy, fmt) or ops.quantize_rows(dy, fmt, want_colsum=True, want_rownorm=True)
-    # (round 6) the GELU-backward epilogue of the input-gradient GEMM reads the kept e4m3 pre-activation anyway: it also emits the
-    # activation operand of this layer's weight gradient (ops.gemm_nt_f8_emit) - the weight gradient then follows the input gradient
-    fuse_emit = g is None and hpre is not None and hpre.dtype == torch.uint8 and not (fmt == ops.FMT_E4M3 and cfg.get("fp8_predict"))
-    if not fuse_emit:
-        emit_g = (lambda r, t: ops.scale_quantize_rows(g, r, t)) if g is not None else (lambda r, t: ops.scale_quantize_rows(hpre, r, t, act=act))
-        d_w_proj = _wgrad8(dq, ds, sg, emit_g, P["dt_w_proj"], cfg)
-    del g
-    if fuse_emit:
+    # y = x1 + c_proj(gelu(hpre)); (dq, ds, colsum[, rownorm: the predicted scales only])
+    q8 = cfg.handoff.take(dy, fmt) or ops.quantize_rows(dy, fmt, want_colsum=True, want_rownorm=cfg.predict)
+    dq, ds, d_b_proj = q8[:3]
+    predict_dh = cfg.predict and fmt == ops.FMT_E4M3
+    if hpre.dtype == torch.uint8 and not predict_dh:
+        # (round 6) the GELU-backward epilogue of the input-gradient GEMM reads the kept e4m3 pre-activation anyway: it also emits the
+        # activation operand of this layer's weight gradient (ops.gemm_nt_f8_emit) - the weight gradient then follows the input gradient
         t = ops.rowscale_max(ds, sg)
         wq, ws = P["wt8_proj"]
         dh, x8 = ops.gemm_nt_f8_emit(dq, ds, wq, ws, hpre, t, act=act, fmt_a=fmt)
@@ -286,23 +270,23 @@ def _block_backward_fp8(x, dy, box, P, cfg, scales):
         del x8
         dq, ds, d_b_fc = _gradq8(dh, cfg)
         del dh
-    elif fmt == ops.FMT_E4M3 and cfg.get("fp8_predict"):
-        # the gradient of the pre-activation leaves the GEMM as the e4m3 operand of the next two products, with its column sums
-        # (the bias gradient of c_fc) from the same epilogue; row scale predicted as in the forward: |dh[m,c]| <=
-        # ||dy[m,:]|| * max_c ||W_proj[:,c]|| * max gelu' (1.13), times 1.13 for the operands' rounding
-        sdh, sodh = ops.row_bound(rn, P["wn_projT"], None, 1.13 * 1.13)
-        dq, d_b_fc = _dlin8(dq, ds, P, "proj", cfg, epi=ops.EPI_DACT, act=act, aux=hpre, out_scale=sodh, want_colsum=True)
-        ds = sdh
-    else:   # e5m2 gradient bytes: bf16 gradient + the row quantiser
-        dh = _dlin8(dq, ds, P, "proj", cfg, epi=ops.EPI_DACT, act=act, aux=hpre)     # [M,4D]
-        dq, ds, d_b_fc = _gradq8(dh, cfg)
-        del dh
-    del hpre
-    emit_h2 = (lambda r, t: ops.scale_quantize_rows(h2, r, t)) if h2 is not None else \
-        (lambda r, t: ops.layernorm_fwd_q8s(x1, P["ln2_w"], P["ln2_b"], r, t, eps))
-    d_w_fc = _wgrad8(dq, ds, s2, emit_h2, P["dt_w_fc"], cfg)
+    else:
+        d_w_proj = _wgrad8(dq, ds, sg, lambda r, t: ops.scale_quantize_rows(hpre, r, t, act=act), P["dt_w_proj"], cfg)
+        if predict_dh:
+            # the gradient of the pre-activation leaves the GEMM as the e4m3 operand of the next two products, with its column
+            # sums (the bias gradient of c_fc) from the same epilogue; row scale predicted as in the forward: |dh[m,c]| <=
+            # ||dy[m,:]|| * max_c ||W_proj[:,c]|| * max gelu' (1.13), times 1.13 for the operands' rounding
+            sdh, sodh = ops.row_bound(q8[3], P["wn_projT"], None, 1.13 * 1.13)
+            dq, d_b_fc = _dlin8(dq, ds, P, "proj", cfg, epi=ops.EPI_DACT, act=act, aux=hpre, out_scale=sodh, want_colsum=True)
+            ds = sdh
+        else:   # bf16 gradient + the row quantiser
+            dh = _dlin8(dq, ds, P, "proj", cfg, epi=ops.EPI_DACT, act=act, aux=hpre)     # [M,4D]
+            dq, ds, d_b_fc = _gradq8(dh, cfg)
+            del dh
+    del hpre, q8
+    d_w_fc = _wgrad8(dq, ds, s2, lambda r, t: ops.layernorm_fwd_q8s(x1, P["ln2_w"], P["ln2_b"], r, t, eps), P["dt_w_fc"], cfg)
     dh2 = _dlin8(dq, ds, P, "fc", cfg)                                            # [M,D]
-    del dq, ds, h2
+    del dq, ds
     # (round 6) the two LayerNorm backwards hand the next product its fp8 operand themselves: the rows are in registers
     dx1, d_ln2_w, d_ln2_b, (dq, ds, d_b_out) = ops.layernorm_bwd(x1, P["ln2_w"], dh2, dres=dy, eps=eps, q8_fmt=fmt)
     del dh2, x1
@@ -314,14 +298,12 @@ def _block_backward_fp8(x, dy, box, P, cfg, scales):
     del da, a, qkv, stats
     dq, ds, d_b_in = _gradq8(dqkv, cfg)
     del dqkv
-    emit_h1 = (lambda r, t: ops.scale_quantize_rows(h1, r, t)) if h1 is not None else \
-        (lambda r, t: ops.layernorm_fwd_q8s(x, P["ln1_w"], P["ln1_b"], r, t, eps))
-    d_w_in = _wgrad8(dq, ds, s1, emit_h1, P["dt_w_in"], cfg)
+    d_w_in = _wgrad8(dq, ds, s1, lambda r, t: ops.layernorm_fwd_q8s(x, P["ln1_w"], P["ln1_b"], r, t, eps), P["dt_w_in"], cfg)
     dh1 = _dlin8(dq, ds, P, "in", cfg)
-    del dq, ds, h1
-    if cfg.get("q8_handoff"):      # the block in front of this one runs the same engine: its backward starts from (q, dq, colsum, rownorm)
-        dx, d_ln1_w, d_ln1_b, q8 = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=dx1, eps=eps, q8_fmt=fmt, want_rownorm=True)
-        _q8_offer(dx, q8, fmt)
+    del dq, ds
+    if offer:      # the block in front of this one runs the same engine: its backward starts from (q, dq, colsum[, rownorm])
+        dx, d_ln1_w, d_ln1_b, q8 = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=dx1, eps=eps, q8_fmt=fmt, want_rownorm=cfg.predict)
+        cfg.handoff.offer(dx, q8, fmt)
     else:
         dx, d_ln1_w, d_ln1_b = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=dx1, eps=eps)
     return dx, (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out, d_ln2_w, d_ln2_b, d_w_fc, d_b_fc, d_w_proj,
@@ -331,19 +313,19 @@ def _block_backward_fp8(x, dy, box, P, cfg, scales):
 def _block_backward(x, dy, box, P, cfg):
     """box: one-element list holding the intermediates tuple (popped so they can be freed early).  bf16 engines (the fp8 engine:
     _block_backward_fp8)."""
-    B, L, H, causal, act = cfg["B"], cfg["L"], cfg["H"], cfg["causal"], cfg["act"]
+    act = cfg.act
     h1, qkv, a, stats, x1, h2, hpre, g = box.pop()
     dy = dy.contiguous()
     # tensors the block did not keep are recomputed here, bit for bit as the forward produced them
     if qkv is None:
-        h1 = ops.layernorm_fwd(x, P["ln1_w"], P["ln1_b"], cfg["eps"])
+        h1 = ops.layernorm_fwd(x, P["ln1_w"], P["ln1_b"], cfg.eps)
         qkv = ops.gemm_nt(h1, P["w_in"], P["b_in"])
     if a is None:
         a, stats = _attn_fwd(qkv, cfg, True)
     if x1 is None:
         x1 = ops.gemm_nt(a, P["w_out"], P["b_out"], epi=ops.EPI_ADD, aux=x)
     if hpre is None:     # "medium" block: LN2 + c_fc again (one GEMM instead of four + attention)
-        h2 = ops.layernorm_fwd(x1, P["ln2_w"], P["ln2_b"], cfg["eps"])
+        h2 = ops.layernorm_fwd(x1, P["ln2_w"], P["ln2_b"], cfg.eps)
         g, hpre = ops.gemm_nt(h2, P["w_fc"], P["b_fc"], epi=ops.EPI_ACT, act=act, want_pre=True)
     # "light8" block: the GELU-backward epilogue below reads the e4m3 bytes anyway and writes act(hpre) beside its own output
     # (round 6: one more store per chunk instead of an HBM-bound pass over the same bytes; bit for bit what activation_fwd writes)
@@ -370,14 +352,14 @@ def _block_backward(x, dy, box, P, cfg):
         del hpre
     dh2 = ops.gemm_nt(dh, P["wt_fc"])       # [M,D]
     if emit2:
-        dx1, d_ln2_w, d_ln2_b, h2 = ops.layernorm_bwd(x1, P["ln2_w"], dh2, dres=dy, eps=cfg["eps"], beta=P["ln2_b"])
+        dx1, d_ln2_w, d_ln2_b, h2 = ops.layernorm_bwd(x1, P["ln2_w"], dh2, dres=dy, eps=cfg.eps, beta=P["ln2_b"])
         del dh2, x1
         d_w_fc, d_b_fc = ops.gemm_tn(dh, h2, P["dt_w_fc"], want_colsum=True)
         del dh, h2
     else:
         d_w_fc, d_b_fc = ops.gemm_tn(dh, h2, P["dt_w_fc"], want_colsum=True)
         del dh, h2
-        dx1, d_ln2_w, d_ln2_b = ops.layernorm_bwd(x1, P["ln2_w"], dh2, dres=dy, eps=cfg["eps"])
+        dx1, d_ln2_w, d_ln2_b = ops.layernorm_bwd(x1, P["ln2_w"], dh2, dres=dy, eps=cfg.eps)
         del dh2, x1
     # x1 = x + out_proj(a)
     da = ops.gemm_nt(dx1, P["wt_out"])
@@ -386,22 +368,18 @@ def _block_backward(x, dy, box, P, cfg):
     del da, a, qkv, stats
     dh1 = ops.gemm_nt(dqkv, P["wt_in"])
     if emit1:
-        dx, d_ln1_w, d_ln1_b, h1 = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=dx1, eps=cfg["eps"], beta=P["ln1_b"])
+        dx, d_ln1_w, d_ln1_b, h1 = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=dx1, eps=cfg.eps, beta=P["ln1_b"])
         d_w_in, d_b_in = ops.gemm_tn(dqkv, h1, P["dt_w_in"], want_colsum=True)
         del dqkv, h1
     else:
         d_w_in, d_b_in = ops.gemm_tn(dqkv, h1, P["dt_w_in"], want_colsum=True)
         del dqkv, h1
-        dx, d_ln1_w, d_ln1_b = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=dx1, eps=cfg["eps"])
+        dx, d_ln1_w, d_ln1_b = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=dx1, eps=cfg.eps)
     return dx, (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out, d_ln2_w, d_ln2_b, d_w_fc, d_b_fc, d_w_proj,
                 d_b_proj)
 
 
-BLOCK_PARAM_ORDER = ("ln1_w", "ln1_b", "w_in", "b_in", "w_out", "b_out", "ln2_w", "ln2_b", "w_fc", "b_fc", "w_proj",
-                     "b_proj")
-
-
-def _block_operands(params, cache, fp8=False, fp8_names=("in", "out", "fc", "proj")):
+def _block_operands(params, cache, cfg, fp8_names=("in", "out", "fc", "proj")):
     ln1_w, ln1_b, w_in, b_in, w_out, b_out, ln2_w, ln2_b, w_fc, b_fc, w_proj, b_proj = params
     P = {
         "ln1_w": cache.f32(ln1_w), "ln1_b": cache.f32(ln1_b), "ln2_w": cache.f32(ln2_w), "ln2_b": cache.f32(ln2_b),
@@ -410,16 +388,15 @@ def _block_operands(params, cache, fp8=False, fp8_names=("in", "out", "fc", "pro
         "b_in": cache.f32(b_in), "b_out": cache.f32(b_out), "b_fc": cache.f32(b_fc), "b_proj": cache.f32(b_proj),
         "dt_w_in": w_in.dtype, "dt_w_out": w_out.dtype, "dt_w_fc": w_fc.dtype, "dt_w_proj": w_proj.dtype,
     }
-    if fp8:   # e4m3 copies, one scale per output channel of the GEMM they feed (rows of W forward, rows of W^T backward); only
+    if cfg.fp8:   # e4m3 copies, one scale per output channel of the GEMM they feed (rows of W forward, rows of W^T backward); only
         # of the layers that run on the fp8 path (LastBlockFn: the in-projection alone - its B pooled rows take the bf16 GEMMs)
         for name, w in (("in", w_in), ("out", w_out), ("fc", w_fc), ("proj", w_proj)):
             if name not in fp8_names:
                 continue
             P["w8_" + name] = cache.custom(w, "w8", lambda t, w=w: ops.quantize_rows(cache.w(w)))
             P["wt8_" + name] = cache.custom(w, "wt8", lambda t, w=w: ops.quantize_rows(cache.wt(w)))
-        P["one"] = cache.custom(w_in, "one", lambda t: torch.ones(1, device=t.device, dtype=f32))
-        if "fc" in fp8_names:
-            # the two scalars per layer behind the PREDICTED row scales of the MLP's 4 D-wide products (_row_bound): the largest
+        if cfg.predict and "fc" in fp8_names:
+            # the two scalars per layer behind the PREDICTED row scales of the MLP's 4 D-wide products (ops.row_bound): the largest
             # row norm of c_fc.weight and |c_fc.bias| bound the pre-activation, the largest row norm of c_proj.weight^T the
             # gradient that comes back through c_proj; device scalars, refreshed with the operand copies once per optimizer step
             P["wn_fc"] = cache.custom(w_fc, "wn", lambda t: ops.rownorm_max(cache.w(w_fc)))
@@ -433,16 +410,12 @@ class ResBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, cfg, cache, *params):
-        P = _block_operands(params, cache, bool(cfg.get("fp8")))
+        P = _block_operands(params, cache, cfg)
         needs_grad = any(ctx.needs_input_grad)
-        keep = False
-        if needs_grad:
-            keep = cfg.get("keep", "light") if (not cfg["recompute"] or cfg.get("keep_this", False)) else False
-        ctx.scales = None
-        if cfg.get("fp8"):
+        keep = cfg.keep if needs_grad else frozenset()
+        if cfg.fp8:
             y, inter, scales = _block_forward_fp8(x, P, cfg, keep)
-            if needs_grad:
-                ctx.scales = scales
+            ctx.scales = scales if needs_grad else None
         else:
             y, inter = _block_forward(x, P, cfg, keep)
         ctx.cfg, ctx.cache, ctx.params = cfg, cache, params
@@ -455,16 +428,16 @@ class ResBlockFn(torch.autograd.Function):
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         cfg, params = ctx.cfg, ctx.params
-        P = _block_operands(params, ctx.cache, bool(cfg.get("fp8")))
+        P = _block_operands(params, ctx.cache, cfg)
         box = [ctx.inter]
         ctx.inter = None
-        if cfg.get("fp8"):
+        if cfg.fp8:
             scales, ctx.scales = ctx.scales, None
-            box[0] = _fp8_fill(x, box[0] if box[0] is not None else (None,) * 8, P, cfg)
-            dx, grads = _block_backward_fp8(x, dy, box, P, cfg, scales)
+            box[0] = _fp8_fill(x, box[0], P, cfg)
+            dx, grads = _block_backward_fp8(x, dy, box, P, cfg, scales, offer=cfg.offer and ctx.needs_input_grad[0])
         else:
             if box[0] is None:
-                box[0] = _block_forward(x, P, cfg, True, need_y=False)[1]
+                box[0] = _block_forward(x, P, cfg, _KEEP_ALL, need_y=False)[1]
             dx, grads = _block_backward(x, dy, box, P, cfg)
         grads = tuple(_like_param(g, p) if p.requires_grad else None for g, p in zip(grads, params))
         return (dx, None, None) + grads
@@ -486,38 +459,35 @@ class LastBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, rows, cfg, cache, *params):
-        P = _block_operands(params, cache, bool(cfg.get("fp8")), fp8_names=("in",))
+        P = _block_operands(params, cache, cfg, fp8_names=("in",))
         needs_grad = any(ctx.needs_input_grad)
         # token-level tensors this block keeps: the block's keep set like any other block's ("qkv", "a" = attention output +
-        # softmax statistics; the named tiers all hold both); x1 / the pre-activation exist for the B pooled rows only
-        ks = frozenset()
-        if needs_grad and (not cfg["recompute"] or cfg.get("keep_this", False)):
-            keep = cfg.get("keep", "light")
-            ks = KEEP_SETS.get(keep, keep) if isinstance(keep, (str, frozenset)) else KEEP_SETS["light"]
+        # softmax statistics); x1 / the pre-activation exist for the B pooled rows only
+        keep = cfg.keep if needs_grad else frozenset()
         s1_box = [None]
-        qkv, a, stats = LastBlockFn._tokens(x, P, cfg, "a" in ks, box=s1_box)
+        qkv, a, stats = LastBlockFn._tokens(x, P, cfg, "a" in keep, box=s1_box)
         ctx.s1 = s1_box[0] if needs_grad else None
         a_c, x_c = ops.gather_rows(a, rows), ops.gather_rows(x, rows)
         x1 = ops.gemm_nt(a_c, P["w_out"], P["b_out"], epi=ops.EPI_ADD, aux=x_c)
-        h2 = ops.layernorm_fwd(x1, P["ln2_w"], P["ln2_b"], cfg["eps"])
-        g, hpre = ops.gemm_nt(h2, P["w_fc"], P["b_fc"], epi=ops.EPI_ACT, act=cfg["act"], want_pre=True)
+        h2 = ops.layernorm_fwd(x1, P["ln2_w"], P["ln2_b"], cfg.eps)
+        g, hpre = ops.gemm_nt(h2, P["w_fc"], P["b_fc"], epi=ops.EPI_ACT, act=cfg.act, want_pre=True)
         y = ops.gemm_nt(g, P["w_proj"], P["b_proj"], epi=ops.EPI_ADD, aux=x1)
         ctx.cfg, ctx.cache, ctx.params = cfg, cache, params
         if needs_grad:
             ctx.save_for_backward(x, rows)
-            ctx.tokens = (qkv if "qkv" in ks else None, a if "a" in ks else None, stats if "a" in ks else None)
+            ctx.tokens = (qkv if "qkv" in keep else None, a if "a" in keep else None, stats)
             ctx.small = (a_c, x1, h2, hpre, g)
         return y
 
     @staticmethod
     def _qkv(x, P, cfg, box=None):
         """-> qkv; fp8 engines leave the LayerNorm output's per-token scale in box[0] (the weight gradient's tensor scale, _wgrad8)."""
-        if cfg.get("fp8"):
-            _, q1, s1 = ops.layernorm_fwd_q8(x, P["ln1_w"], P["ln1_b"], cfg["eps"], want_bf16=False)
+        if cfg.fp8:
+            _, q1, s1 = ops.layernorm_fwd_q8(x, P["ln1_w"], P["ln1_b"], cfg.eps)
             if box is not None:
                 box[0] = s1
             return _lin8(q1, s1, P, "in")
-        return ops.gemm_nt(ops.layernorm_fwd(x, P["ln1_w"], P["ln1_b"], cfg["eps"]), P["w_in"], P["b_in"])
+        return ops.gemm_nt(ops.layernorm_fwd(x, P["ln1_w"], P["ln1_b"], cfg.eps), P["w_in"], P["b_in"])
 
     @staticmethod
     def _tokens(x, P, cfg, want_stats, qkv=None, box=None):
@@ -530,16 +500,16 @@ class LastBlockFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, rows = ctx.saved_tensors
         cfg, params = ctx.cfg, ctx.params
-        P = _block_operands(params, ctx.cache, bool(cfg.get("fp8")), fp8_names=("in",))
+        P = _block_operands(params, ctx.cache, cfg, fp8_names=("in",))
         a_c, x1, h2, hpre, g = ctx.small
         ctx.small = None
         dy = dy.contiguous()
         M = x.shape[0]
-        dh = ops.gemm_nt(dy, P["wt_proj"], epi=ops.EPI_DACT, act=cfg["act"], aux=hpre)
+        dh = ops.gemm_nt(dy, P["wt_proj"], epi=ops.EPI_DACT, act=cfg.act, aux=hpre)
         d_w_proj, d_b_proj = ops.gemm_tn(dy, g, P["dt_w_proj"], want_colsum=True)
         dh2 = ops.gemm_nt(dh, P["wt_fc"])
         d_w_fc, d_b_fc = ops.gemm_tn(dh, h2, P["dt_w_fc"], want_colsum=True)
-        dx1, d_ln2_w, d_ln2_b = ops.layernorm_bwd(x1, P["ln2_w"], dh2, dres=dy, eps=cfg["eps"])
+        dx1, d_ln2_w, d_ln2_b = ops.layernorm_bwd(x1, P["ln2_w"], dh2, dres=dy, eps=cfg.eps)
         da_c = ops.gemm_nt(dx1, P["wt_out"])
         d_w_out, d_b_out = ops.gemm_tn(dx1, a_c, P["dt_w_out"], want_colsum=True)
         (qkv, a, stats), ctx.tokens = ctx.tokens, None
@@ -548,21 +518,21 @@ class LastBlockFn(torch.autograd.Function):
             a, stats = a2, stats2
         dqkv = _attn_bwd(qkv, a, ops.scatter_rows(da_c, rows, M), stats, cfg)
         del qkv, a, stats
-        if cfg.get("fp8"):      # token-level products of the block on the fp8 path: input and weight gradient of the in-projection
+        if cfg.fp8:      # token-level products of the block on the fp8 path: input and weight gradient of the in-projection
             s1, ctx.s1 = ctx.s1, None
             dq, ds, d_b_in = _gradq8(dqkv, cfg)
             del dqkv
-            d_w_in = _wgrad8(dq, ds, s1, lambda r, t: ops.layernorm_fwd_q8s(x, P["ln1_w"], P["ln1_b"], r, t, cfg["eps"]),
+            d_w_in = _wgrad8(dq, ds, s1, lambda r, t: ops.layernorm_fwd_q8s(x, P["ln1_w"], P["ln1_b"], r, t, cfg.eps),
                              P["dt_w_in"], cfg)
             dh1 = _dlin8(dq, ds, P, "in", cfg)
             del dq, ds
         else:
             dh1 = ops.gemm_nt(dqkv, P["wt_in"])
-            h1 = ops.layernorm_fwd(x, P["ln1_w"], P["ln1_b"], cfg["eps"])
+            h1 = ops.layernorm_fwd(x, P["ln1_w"], P["ln1_b"], cfg.eps)
             d_w_in, d_b_in = ops.gemm_tn(dqkv, h1, P["dt_w_in"], want_colsum=True)
             del dqkv, h1
         # x1 = x[rows] + out_proj(a[rows]): the residual gradient reaches x at the pooled rows only
-        dx, d_ln1_w, d_ln1_b = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=ops.scatter_rows(dx1, rows, M), eps=cfg["eps"])
+        dx, d_ln1_w, d_ln1_b = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=ops.scatter_rows(dx1, rows, M), eps=cfg.eps)
         grads = (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out, d_ln2_w, d_ln2_b, d_w_fc, d_b_fc, d_w_proj, d_b_proj)
         grads = tuple(_like_param(gr, p) if p.requires_grad else None for gr, p in zip(grads, params))
         return (dx, None, None, None) + grads
@@ -579,11 +549,16 @@ def _conv_weight_operand(w, Kp):
     return ops.to_bf16(m.contiguous())
 
 
+# VisionStemFn: B images of L tokens, P x P patches (K = 3 P P zero-padded to Kp), mean / std of uint8 images (None: float
+# input), whether ln_pre exists
+StemCfg = collections.namedtuple("StemCfg", "B L P Kp eps ln_pre mean std")
+
+
 def _vision_stem_forward(image, P, cfg):
-    patches = ops.patchify(image, cfg["P"], cfg["Kp"], cfg["mean"], cfg["std"])
+    patches = ops.patchify(image, cfg.P, cfg.Kp, cfg.mean, cfg.std)
     pe = ops.gemm_nt(patches, P["w_conv"])
-    tok = ops.assemble_tokens(pe, P["cls"], P["pos"], cfg["B"], cfg["L"])
-    x0 = ops.layernorm_fwd(tok, P["ln_w"], P["ln_b"], cfg["eps"]) if cfg["ln_pre"] else tok
+    tok = ops.assemble_tokens(pe, P["cls"], P["pos"], cfg.B, cfg.L)
+    x0 = ops.layernorm_fwd(tok, P["ln_w"], P["ln_b"], cfg.eps) if cfg.ln_pre else tok
     return patches, tok, x0
 
 
@@ -602,10 +577,10 @@ class VisionStemFn(torch.autograd.Function):
 
     @staticmethod
     def _operands(cfg, cache, conv_w, cls, pos, ln_w, ln_b):
-        Kp = cfg["Kp"]
+        Kp = cfg.Kp
         P = {"w_conv": cache.custom(conv_w, "conv%d" % Kp, lambda t: _conv_weight_operand(t, Kp)),
              "cls": cache.f32(cls), "pos": cache.f32(pos)}
-        if cfg["ln_pre"]:
+        if cfg.ln_pre:
             P["ln_w"], P["ln_b"] = cache.f32(ln_w), cache.f32(ln_b)
         return P
 
@@ -618,11 +593,11 @@ class VisionStemFn(torch.autograd.Function):
         patches, tok, _ = _vision_stem_forward(image, P, cfg)
         dx0 = dx0.contiguous()
         d_ln_w = d_ln_b = None
-        if cfg["ln_pre"]:
-            dtok, d_ln_w, d_ln_b = ops.layernorm_bwd(tok, P["ln_w"], dx0, eps=cfg["eps"])
+        if cfg.ln_pre:
+            dtok, d_ln_w, d_ln_b = ops.layernorm_bwd(tok, P["ln_w"], dx0, eps=cfg.eps)
         else:
             dtok = dx0
-        dpatch, dcls, dpos = ops.assemble_tokens_bwd(dtok, cfg["B"], cfg["L"], need_pos=pos.requires_grad)
+        dpatch, dcls, dpos = ops.assemble_tokens_bwd(dtok, cfg.B, cfg.L, need_pos=pos.requires_grad)
         d_conv = None
         if conv_w.requires_grad:
             D, C, Pp, _ = conv_w.shape
@@ -633,8 +608,8 @@ class VisionStemFn(torch.autograd.Function):
         return (None, None, None, d_conv,
                 _like_param(dcls, cls) if cls.requires_grad else None,
                 _like_param(dpos, pos) if pos.requires_grad else None,
-                _like_param(d_ln_w, ln_w) if (cfg["ln_pre"] and ln_w.requires_grad) else None,
-                _like_param(d_ln_b, ln_b) if (cfg["ln_pre"] and ln_b.requires_grad) else None)
+                _like_param(d_ln_w, ln_w) if (cfg.ln_pre and ln_w.requires_grad) else None,
+                _like_param(d_ln_b, ln_b) if (cfg.ln_pre and ln_b.requires_grad) else None)
 
 
 class TokenDropFn(torch.autograd.Function):
@@ -675,15 +650,18 @@ class TextStemFn(torch.autograd.Function):
                 _like_param(dpos, pos) if pos.requires_grad else None)
 
 
+HeadCfg = collections.namedtuple("HeadCfg", "B L mode eps")      # HeadFn: B samples of L rows, pooled by ops.POOL_* `mode`
+
+
 class HeadFn(torch.autograd.Function):
     """pool -> LayerNorm -> @ proj, returning f32 features [B,E].  Pooling commutes with the per-token
     LayerNorm, so LN runs on B rows instead of B*L (SURVEY 8a identity 8)."""
 
     @staticmethod
     def forward(ctx, x, idx, cfg, cache, ln_w, ln_b, proj):
-        B, L, mode = cfg["B"], cfg["L"], cfg["mode"]
+        B, L, mode = cfg.B, cfg.L, cfg.mode
         pooled = ops.pool_fwd(x, B, L, mode, idx)                            # f32 [B,D]
-        y = ops.layernorm_fwd(pooled, cache.f32(ln_w), cache.f32(ln_b), cfg["eps"], out_dtype=bf16)
+        y = ops.layernorm_fwd(pooled, cache.f32(ln_w), cache.f32(ln_b), cfg.eps, out_dtype=bf16)
         feat = ops.gemm_nt(y, cache.wt(proj), out_f32=True) if proj is not None else ops.to_f32(y)
         ctx.cfg, ctx.cache, ctx.params = cfg, cache, (ln_w, ln_b, proj)
         ctx.save_for_backward(pooled, y, idx if idx is not None else torch.empty(0, device=x.device))
@@ -704,8 +682,8 @@ class HeadFn(torch.autograd.Function):
                 d_proj = _like_param(ops.gemm_tn(y, dfb, f32), proj)          # [D,E]
         else:
             dy = dfb
-        dpooled, d_ln_w, d_ln_b = ops.layernorm_bwd(pooled, cache.f32(ln_w), dy, eps=cfg["eps"])
-        dx = ops.pool_bwd(dpooled, cfg["B"], cfg["L"], cfg["mode"], idx)
+        dpooled, d_ln_w, d_ln_b = ops.layernorm_bwd(pooled, cache.f32(ln_w), dy, eps=cfg.eps)
+        dx = ops.pool_bwd(dpooled, cfg.B, cfg.L, cfg.mode, idx)
         return (dx, None, None, None,
                 _like_param(d_ln_w, ln_w) if ln_w.requires_grad else None,
                 _like_param(d_ln_b, ln_b) if ln_b.requires_grad else None,

@@ -11,7 +11,7 @@ forward and backward runs in libclipa_hip.so via clipa_amd.engine.
 """
 import math
 from collections import OrderedDict
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Optional, Tuple, Union
 
 import os
@@ -135,6 +135,19 @@ class _ResBlockParams(nn.Module):
         raise RuntimeError("parameter holder: computed by clipa_amd.engine.ResBlockFn")
 
 
+# What a block keeps for its backward besides its input (engine.BlockCfg.keep): "light" = the GEMM / attention outputs qkv, a
+# (with the softmax statistics), x1 and the bf16 MLP pre-activation h - the LayerNorm outputs and the activation are
+# re-materialised in backward; "light8" = light with h as saturating e4m3 bytes written by the c_fc epilogue itself (14 instead
+# of 18 bytes per element of x; the backward takes gelu'(h) and the activation from the e4m3 value - ~3 % rms rounding of h, the
+# only tier whose gradients are not bit-identical to the recomputed block's); "medium" = light without h (10 bytes per element
+# of x: backward re-runs LN2 + the c_fc GEMM, a third of the block's forward FLOPs, and skips the other three GEMMs and
+# attention).  keep_counts names the same tensors one by one (round 4: what a byte buys differs per tensor - the e4m3
+# pre-activation ~1.5 ms per GB, the attention output ~0.94, x1 ~0.91, qkv ~0.79 at ViT-L/16 - so bench.py's planner keeps them
+# independently).
+KEEP_SETS = {"light": frozenset(("qkv", "a", "x1", "h")), "light8": frozenset(("qkv", "a", "x1", "h8")),
+             "medium": frozenset(("qkv", "a", "x1"))}
+
+
 class Transformer(nn.Module):
     """transformer.py:294-326: a stack of residual attention blocks over a [B*L, D] token matrix."""
 
@@ -154,7 +167,7 @@ class Transformer(nn.Module):
         self.medium_blocks = 0
         # ... and `light8_blocks` blocks in between keep the light set with the MLP pre-activation as e4m3 bytes (~14*D bytes
         # per token): no GEMM is re-run, gelu'(h) and the re-materialised activation come from the rounded value
-        # (engine._block_forward).  Order of the tiers along the depth: light, light8, medium, recompute.
+        # (KEEP_SETS).  Order of the tiers along the depth: light, light8, medium, recompute.
         self.light8_blocks = 0
         # ... or tensor by tensor (what bench.py's planner uses; fp8 engines too since round 6): the LAST keep_counts[t] blocks keep tensor t (their
         # backward runs first, at the memory peak: the blocks that recompute do so after kept tensors have been released)
@@ -170,6 +183,7 @@ class Transformer(nn.Module):
         # row norm) instead of bf16 + a row quantiser: ~5 % faster, per-tensor gradient cosines 0.001-0.009 lower
         self.fp8_predicted_scales = False
         self.resblocks = nn.ModuleList([_ResBlockParams(width, heads, mlp_ratio) for _ in range(layers)])
+        self._handoff = engine.GradHandoff()      # the fp8 blocks' gradient-operand slot (one per tower)
 
     def get_cast_dtype(self):
         return self.resblocks[0].mlp.c_fc.weight.dtype
@@ -179,26 +193,25 @@ class Transformer(nn.Module):
         returns only them ([B, D]; engine.LastBlockFn)."""
         if causal and self.width // self.heads > 80:
             _unsupported(f"causal attention with head dim {self.width // self.heads} (the wide heads are compiled for image towers)")
-        base = {"B": B, "L": L, "H": self.heads, "causal": bool(causal), "act": self.act, "eps": 1e-5,
-                "recompute": bool(self.grad_checkpointing), "keep": "light", "fp8": bool(self.fp8),
-                "fp8_grad_fmt": ops.FMT_E5M2 if self.fp8_grad_format == "e5m2" else ops.FMT_E4M3,
-                "fp8_predict": bool(self.fp8 and self.fp8_predicted_scales), "varlen": varlen}
-        kept, medium = dict(base, keep_this=True), dict(base, keep_this=True, keep="medium")
-        light8 = dict(base, keep_this=True, keep="light8")
-        n1, n2 = self.keep_blocks, self.keep_blocks + self.light8_blocks
-        last = len(self.resblocks) - 1
-        counted = any(self.keep_counts.values())
+        self._handoff.clear()      # an offer no block backward took (a frozen prefix, an exception) ends with the step
+        base = engine.BlockCfg(B=B, L=L, H=self.heads, causal=bool(causal), act=self.act, eps=1e-5, varlen=varlen,
+                               fp8=bool(self.fp8), grad_fmt=ops.FMT_E5M2 if self.fp8_grad_format == "e5m2" else ops.FMT_E4M3,
+                               predict=bool(self.fp8 and self.fp8_predicted_scales), keep=frozenset(),
+                               handoff=self._handoff if self.fp8 else None, offer=False)
+        n = len(self.resblocks)
+        tiers = [KEEP_SETS["light"]] * self.keep_blocks + [KEEP_SETS["light8"]] * self.light8_blocks + \
+            [KEEP_SETS["medium"]] * self.medium_blocks
+        unplanned = frozenset() if self.grad_checkpointing else KEEP_SETS["light"]
+        cfgs = {}
         for i, blk in enumerate(self.resblocks):
-            cfg = kept if i < n1 else (light8 if i < n2 else (medium if i < n2 + self.medium_blocks else base))
-            if counted:
-                ks = frozenset(t for t, n in self.keep_counts.items() if i >= len(self.resblocks) - n) | engine.KEEP_SETS.get(cfg["keep"] if cfg is not base else None, frozenset())
-                if ks:
-                    cfg = dict(base, keep_this=True, keep=ks)
-            if self.fp8 and i > 0:      # this block's LayerNorm-1 backward hands block i-1 its incoming gradient as fp8 operand
-                cfg = dict(cfg, q8_handoff=True)
-            if i == last and pooled_rows is not None:
-                return engine.LastBlockFn.apply(x, pooled_rows, cfg, cache, *blk.param_tuple())
-            x = engine.ResBlockFn.apply(x, cfg, cache, *blk.param_tuple())
+            keep = (tiers[i] if i < len(tiers) else frozenset()) | {t for t, c in self.keep_counts.items() if i >= n - c}
+            # (an fp8 block's LayerNorm-1 backward hands block i-1 its incoming gradient as fp8 operand)
+            plan = (keep or unplanned, bool(self.fp8) and i > 0)
+            if plan not in cfgs:
+                cfgs[plan] = replace(base, keep=plan[0], offer=plan[1])
+            if i == n - 1 and pooled_rows is not None:
+                return engine.LastBlockFn.apply(x, pooled_rows, cfgs[plan], cache, *blk.param_tuple())
+            x = engine.ResBlockFn.apply(x, cfgs[plan], cache, *blk.param_tuple())
         return x if pooled_rows is None else engine.TokenDropFn.apply(x, pooled_rows)
 
     def light_keep_bytes(self, tokens):
@@ -308,9 +321,9 @@ class VisionTransformer(nn.Module):
                                f"{self.positional_embedding.shape[0]} rows")
         k = 3 * Pp * Pp
         has_ln_pre = isinstance(self.ln_pre, nn.LayerNorm)
-        cfg = {"B": B, "L": L, "P": Pp, "Kp": (k + 7) // 8 * 8, "eps": 1e-5, "ln_pre": has_ln_pre,
-               "mean": self.image_mean if x.dtype == torch.uint8 else None,
-               "std": self.image_std if x.dtype == torch.uint8 else None}
+        cfg = engine.StemCfg(B=B, L=L, P=Pp, Kp=(k + 7) // 8 * 8, eps=1e-5, ln_pre=has_ln_pre,
+                             mean=self.image_mean if x.dtype == torch.uint8 else None,
+                             std=self.image_std if x.dtype == torch.uint8 else None)
         ln_w = self.ln_pre.weight if has_ln_pre else self.class_embedding
         ln_b = self.ln_pre.bias if has_ln_pre else self.class_embedding
         x0 = engine.VisionStemFn.apply(x, cfg, self._cache, self.conv1.weight, self.class_embedding,
@@ -326,10 +339,10 @@ class VisionTransformer(nn.Module):
             # the head reads the class token only: the last block computes that row alone (engine.LastBlockFn)
             rows = torch.arange(B, device=x0.device, dtype=torch.int64) * L
             xc = self.transformer.run(x0, B, L, False, self._cache, pooled_rows=rows)
-            hcfg = {"B": B, "L": 1, "mode": ops.POOL_FIRST, "eps": 1e-5}
+            hcfg = engine.HeadCfg(B=B, L=1, mode=ops.POOL_FIRST, eps=1e-5)
             return engine.HeadFn.apply(xc, None, hcfg, self._cache, self.ln_post.weight, self.ln_post.bias, self.proj)
         xL = self.transformer.run(x0, B, L, False, self._cache)
-        hcfg = {"B": B, "L": L, "mode": self._pool_mode(), "eps": 1e-5}
+        hcfg = engine.HeadCfg(B=B, L=L, mode=self._pool_mode(), eps=1e-5)
         return engine.HeadFn.apply(xL, None, hcfg, self._cache, self.ln_post.weight, self.ln_post.bias, self.proj)
 
 
@@ -465,7 +478,7 @@ the host (B integers).  `text_lengths` ([B] integers as a list / tuple / numpy a
             vl = _varlen if _varlen is not None else self._text_varlen(text, text_lengths)
             xp = engine.TokenDropFn.apply(x0, vl.src_rows)
             pooled = self.transformer.run(xp, B, T, True, self._cache, varlen=vl, pooled_rows=vl.last_rows)
-            hcfg = {"B": B, "L": 1, "mode": ops.POOL_FIRST, "eps": 1e-5}
+            hcfg = engine.HeadCfg(B=B, L=1, mode=ops.POOL_FIRST, eps=1e-5)
             features = engine.HeadFn.apply(pooled, None, hcfg, self._cache, self.ln_final.weight, self.ln_final.bias,
                                            self.text_projection)
             return engine.L2NormFn.apply(features) if normalize else features
@@ -478,7 +491,7 @@ the host (B integers).  `text_lengths` ([B] integers as a list / tuple / numpy a
             pos = torch.full((B,), T - 1, device=x0.device, dtype=torch.int64)
         rows = torch.arange(B, device=x0.device, dtype=torch.int64) * T + pos
         pooled = self.transformer.run(x0, B, T, self.causal, self._cache, pooled_rows=rows)
-        hcfg = {"B": B, "L": 1, "mode": ops.POOL_FIRST, "eps": 1e-5}
+        hcfg = engine.HeadCfg(B=B, L=1, mode=ops.POOL_FIRST, eps=1e-5)
         features = engine.HeadFn.apply(pooled, None, hcfg, self._cache, self.ln_final.weight, self.ln_final.bias,
                                        self.text_projection)
         return engine.L2NormFn.apply(features) if normalize else features

@@ -88,6 +88,12 @@ def _chk(t, dtype, name, dims=None):
         raise RuntimeError(f"clipa_amd.ops: {name} must be contiguous in its last dim")
 
 
+def _chk_out_dtype(dtype, name):
+    """The kernels store f32, or bf16 when told so: any other dtype would be allocated and then overrun by the f32 store."""
+    if dtype not in (f32, bf16):
+        raise RuntimeError(f"clipa_amd.ops.{name}: out_dtype must be torch.float32 or torch.bfloat16, got {dtype}")
+
+
 def _rowmajor(t):
     """Accept [rows, cols] views with unit column stride; return (tensor, ld)."""
     if t.stride(-1) != 1:
@@ -190,6 +196,8 @@ def quantize_rows(x, fmt=FMT_E4M3, want_colsum=False, want_rownorm=False):
     """Row-scaled fp8 operand of a bf16 matrix: -> (q uint8 [M,K] holding OCP e4m3 / e5m2 bytes, dq f32 [M]) with
     x[r,:] ~ dq[r] * fp8(q[r,:]).  want_colsum: also sum_r x[r,:] (f32 [K]; the bias gradient when x is a layer's dY);
     want_rownorm (with want_colsum): also ||x[r,:]||_2 (f32 [M]: the row bound of the product this gradient feeds, row_bound)."""
+    if want_rownorm and not want_colsum:
+        raise RuntimeError("clipa_amd.ops.quantize_rows: want_rownorm needs want_colsum")
     _chk(x, bf16, "x", 2)
     x, ld = _rowmajor(x)
     M, K = x.shape
@@ -452,6 +460,7 @@ def layernorm_fwd_q8s(x, gamma, beta, rowscale, t, eps=1e-5):
 def gemm_tn_f8(p8, q8, t=None, alpha=1.0, fmt_p=FMT_E4M3, out_dtype=f32):
     """out[R,C] = alpha * t[0] * p8[M,R]^T @ q8[M,C]; p8 (fmt_p: e4m3 / e5m2), q8 (e4m3) uint8 tensors of fp8 bytes, t an
     optional f32 device scalar."""
+    _chk_out_dtype(out_dtype, "gemm_tn_f8")
     _chk(p8, u8, "p8", 2)
     _chk(q8, u8, "q8", 2)
     p8, ldp = _rowmajor(p8)
@@ -473,6 +482,7 @@ def gemm_tn_f8(p8, q8, t=None, alpha=1.0, fmt_p=FMT_E4M3, out_dtype=f32):
 
 def gemm_tn(p, q, out_dtype=f32, want_colsum=False):
     """out[R,C] = p[M,R]^T @ q[M,C]; p, q bf16.  want_colsum: also return sum_m p[m,:] (f32 [R])."""
+    _chk_out_dtype(out_dtype, "gemm_tn")
     _chk(p, bf16, "p", 2)
     _chk(q, bf16, "q", 2)
     p, ldp = _rowmajor(p)

@@ -306,27 +306,126 @@ def test_encode_entry_points(golden):
         m.encode_text(golden.texts[:, :-1])
 
 
-def test_fp8_gradient_operand_handoff_slot():
-    """engine._q8_offer / _q8_take (round 6): the row-quantised form of a block's input gradient travels beside the tensor to the
+def test_grad_handoff_slot_takes_only_the_offered_tensor():
+    """engine.GradHandoff (round 6): the row-quantised form of a block's input gradient travels beside the tensor to the
     backward of the block in front of it.  It is taken only by the very next fp8 block backward and only for the SAME tensor - same
     storage, shape, strides, dtype, version - in the same gradient format; a copy, a modified tensor or a later backward gets
     nothing and quantises the ordinary way."""
-    from clipa_amd import engine
+    h = engine.GradHandoff()
     dx = torch.randn(8, 16).to(torch.bfloat16)
     q8 = ("q", "dq", "colsum", "rownorm")
-    engine._q8_offer(dx, q8, 0)
-    assert engine._q8_take(dx, 0) is q8
-    assert engine._q8_take(dx, 0) is None                      # one slot, cleared by the take
-    engine._q8_offer(dx, q8, 0)
-    assert engine._q8_take(dx.clone(), 0) is None              # another allocation (a summed / copied gradient)
-    assert engine._q8_take(dx, 0) is None                      # ... and the miss cleared the slot too
-    engine._q8_offer(dx, q8, 0)
-    assert engine._q8_take(dx, 1) is None                      # other gradient format
-    engine._q8_offer(dx, q8, 0)
-    dx.add_(1)                                                 # modified in place after the offer: version counter moved
-    assert engine._q8_take(dx, 0) is None
-    engine._q8_offer(dx, q8, 0)
-    assert engine._q8_take(dx[:4], 0) is None                  # a view of a part: same address, other shape
-    engine._q8_offer(dx, q8, 0)
-    assert engine._q8_take(dx.view(8, 16), 0) is q8            # the same rows through another wrapper object
-    assert engine._Q8_HANDOFF == []
+    h.offer(dx, q8, 0)
+    assert h.take(dx, 0) is q8
+    assert h.take(dx, 0) is None                      # one slot, cleared by the take
+    h.offer(dx, q8, 0)
+    assert h.take(dx.clone(), 0) is None              # another allocation (a summed / copied gradient)
+    assert h.take(dx, 0) is None                      # ... and the miss cleared the slot too
+    h.offer(dx, q8, 0)
+    assert h.take(dx, 1) is None                      # other gradient format
+    h.offer(dx, q8, 0)
+    dx.add_(1)                                        # modified in place after the offer: version counter moved
+    assert h.take(dx, 0) is None
+    h.offer(dx, q8, 0)
+    assert h.take(dx[:4], 0) is None                  # a view of a part: same address, other shape
+    h.offer(dx, q8, 0)
+    assert h.take(dx.view(8, 16), 0) is q8            # the same rows through another wrapper object
+    assert h._slot is None
+
+
+LIGHT, LIGHT8, MEDIUM = model_mod.KEEP_SETS["light"], model_mod.KEEP_SETS["light8"], model_mod.KEEP_SETS["medium"]
+NONE = frozenset()
+
+
+@pytest.mark.parametrize("layers,knobs,want", [
+    (3, dict(grad_checkpointing=False), [LIGHT] * 3),
+    (3, dict(), [NONE] * 3),
+    (5, dict(keep_blocks=1, light8_blocks=1, medium_blocks=1), [LIGHT, LIGHT8, MEDIUM, NONE, NONE]),
+    (4, dict(keep_counts={"a": 2, "qkv": 1}), [NONE, NONE, {"a"}, {"a", "qkv"}]),
+    (4, dict(keep_blocks=2, keep_counts={"h8": 3}), [LIGHT, LIGHT | {"h8"}, {"h8"}, {"h8"}]),
+    (4, dict(medium_blocks=2, keep_counts={"h": 1, "x1": 3}), [MEDIUM, MEDIUM | {"x1"}, {"x1"}, {"h", "x1"}]),
+    (3, dict(grad_checkpointing=False, keep_counts={"x1": 1}), [LIGHT, LIGHT, {"x1"}]),
+])
+@pytest.mark.parametrize("pooled", [False, True])
+def test_transformer_resolves_one_keep_set_per_block(monkeypatch, layers, knobs, want, pooled):
+    """Transformer.run turns grad_checkpointing / keep_blocks / light8_blocks / medium_blocks / keep_counts into the set of
+    tensors each block keeps (the sets the tier names and flags stood for before they were resolved on the model side);
+    LastBlockFn receives its block's set like any other block.  fp8 towers: every block but the first offers its gradient
+    operand to the block in front of it, all through the tower's one hand-off slot."""
+    seen = []
+    monkeypatch.setattr(engine.ResBlockFn, "apply", lambda x, cfg, cache, *p: (seen.append(cfg), x)[1])
+    monkeypatch.setattr(engine.LastBlockFn, "apply", lambda x, rows, cfg, cache, *p: (seen.append(cfg), x)[1])
+    t = model_mod.Transformer(64, layers, 1)
+    t.grad_checkpointing = True
+    for k, v in knobs.items():
+        setattr(t, k, dict(t.keep_counts, **v) if k == "keep_counts" else v)
+    x = torch.zeros(8, 64, dtype=torch.bfloat16)
+    rows = torch.zeros(1, dtype=torch.int64) if pooled else None
+    t.run(x, 1, 8, False, None, pooled_rows=rows)
+    assert [c.keep for c in seen] == [frozenset(w) for w in want]
+    assert all(c.handoff is None and not c.offer and not c.fp8 for c in seen)
+    t.fp8, seen[:] = True, []
+    t.run(x, 1, 8, False, None, pooled_rows=rows)
+    assert [c.keep for c in seen] == [frozenset(w) for w in want]
+    assert [c.offer for c in seen] == [False] + [True] * (layers - 1)
+    assert all(c.fp8 and c.handoff is t._handoff for c in seen)
+
+
+def _fp8_tower(layers=3, seed=0):
+    torch.manual_seed(seed)
+    t = model_mod.Transformer(64, layers, 1)
+    clipa_amd.convert_weights_to_lp(t, torch.bfloat16)
+    t.fp8 = True
+    return t
+
+
+def _record_takes(monkeypatch):
+    """-> list of (hand-off object, hit) per GradHandoff.take."""
+    taken, real_take = [], engine.GradHandoff.take
+
+    def take(self, dy, fmt):
+        r = real_take(self, dy, fmt)
+        taken.append((self, r is not None))
+        return r
+    monkeypatch.setattr(engine.GradHandoff, "take", take)
+    return taken
+
+
+def test_fp8_towers_have_independent_handoff_slots(monkeypatch):
+    """Each tower owns its hand-off slot: an offer in one tower is invisible to the other, and a backward through both towers
+    hands each block's gradient operand over inside its own tower."""
+    ta, tb = _fp8_tower(seed=1), _fp8_tower(seed=2)
+    assert ta._handoff is not tb._handoff
+    dx, q8 = torch.randn(8, 64).to(torch.bfloat16), ("q", "dq", "colsum")
+    ta._handoff.offer(dx, q8, 0)
+    assert tb._handoff.take(dx, 0) is None and ta._handoff.take(dx, 0) is q8
+    taken = _record_takes(monkeypatch)
+    xa = torch.randn(16, 64).to(torch.bfloat16).requires_grad_(True)
+    xb = torch.randn(16, 64).to(torch.bfloat16).requires_grad_(True)
+    ya, yb = ta.run(xa, 2, 8, False, engine.WeightCache()), tb.run(xb, 2, 8, False, engine.WeightCache())
+    (ya.float().square().sum() + yb.float().sum()).backward()
+    for t in (ta, tb):
+        assert [hit for h, hit in taken if h is t._handoff] == [False, True, True]
+        assert t._handoff._slot is None
+
+
+def test_fp8_stale_offer_is_cleared_by_the_next_run():
+    t = _fp8_tower()
+    dx = torch.randn(16, 64).to(torch.bfloat16)
+    t._handoff.offer(dx, ("q", "dq", "colsum"), 0)
+    with torch.no_grad():
+        t.run(torch.randn(16, 64).to(torch.bfloat16), 2, 8, False, engine.WeightCache())
+    assert t._handoff._slot is None
+
+
+def test_fp8_frozen_tower_prefix_leaves_no_offer(monkeypatch):
+    """A locked prefix (block 0 frozen, its input without grad): block 1's backward has no input gradient to hand over, so it
+    offers nothing - no gradient and fp8 operand stay pinned in the slot after the backward."""
+    t = _fp8_tower()
+    for p in t.resblocks[0].parameters():
+        p.requires_grad = False
+    taken = _record_takes(monkeypatch)
+    y = t.run(torch.randn(16, 64).to(torch.bfloat16), 2, 8, False, engine.WeightCache())
+    y.float().square().sum().backward()
+    assert [hit for _, hit in taken] == [False, True]      # block 2 (nothing offered yet), block 1 (block 2's offer)
+    assert t._handoff._slot is None
+    assert t.resblocks[1].mlp.c_fc.weight.grad is not None and t.resblocks[0].mlp.c_fc.weight.grad is None

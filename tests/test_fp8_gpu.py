@@ -652,8 +652,8 @@ def test_layernorm_bwd_with_quantised_output(rows, D, fmt):
             assert all(torch.equal(a, b) for a, b in zip(got[-1], again))      # fixed-order reductions
 
 
-def test_fp8_block_chain_uses_the_handed_over_gradient_operand():
-    """Two fp8 blocks in a row: the second block's LayerNorm-1 backward offers its dx as fp8 operand (engine._q8_offer), the first
+def test_fp8_block_chain_takes_the_operand_from_the_tower_handoff():
+    """Two fp8 blocks in a row: the second block's LayerNorm-1 backward offers its dx as fp8 operand (engine.GradHandoff), the first
     block's backward takes it instead of launching the row quantiser - same gradients as with the hand-off disabled (the bytes
     and scales are identical; the bias gradient of c_proj differs by the order of fp32 additions only)."""
     from clipa_amd import engine
@@ -667,9 +667,9 @@ def test_fp8_block_chain_uses_the_handed_over_gradient_operand():
 
     def run(handoff):
         taken = []
-        real_take, real_offer = engine._q8_take, engine._q8_offer
-        engine._q8_take = lambda dy, fmt: (lambda r: (taken.append(r is not None), r)[1])(real_take(dy, fmt) if handoff else None)
-        engine._q8_offer = real_offer if handoff else (lambda *a: None)
+        real_take, real_offer = engine.GradHandoff.take, engine.GradHandoff.offer
+        engine.GradHandoff.take = lambda self, dy, fmt: (lambda r: (taken.append(r is not None), r)[1])(real_take(self, dy, fmt) if handoff else None)
+        engine.GradHandoff.offer = real_offer if handoff else (lambda *a: None)
         try:
             for p in t.parameters():
                 p.grad = None
@@ -678,7 +678,7 @@ def test_fp8_block_chain_uses_the_handed_over_gradient_operand():
             (y.float() * torch.linspace(-1, 1, y.numel(), device=DEV).reshape(y.shape)).sum().backward()
             return taken, x.grad.clone(), {n: p.grad.clone() for n, p in t.named_parameters()}
         finally:
-            engine._q8_take, engine._q8_offer = real_take, real_offer
+            engine.GradHandoff.take, engine.GradHandoff.offer = real_take, real_offer
     taken, gx, grads = run(True)
     assert taken == [False, True, True], taken          # last block: nothing offered yet; blocks 1 and 0 start from the offer
     taken0, gx0, grads0 = run(False)

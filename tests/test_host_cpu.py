@@ -139,6 +139,20 @@ def test_no_cpu_fallback():
         clipa_amd.ClipLoss()(torch.randn(8, 16), torch.randn(8, 16), torch.tensor(10.0))
 
 
+def test_ops_reject_argument_combinations_they_cannot_serve():
+    """quantize_rows computes row norms only with the column sums (without them it used to return a 2-tuple silently); gemm_tn
+    and gemm_tn_f8 store f32 or bf16 only (any other 2-byte dtype would be allocated and then overrun by the f32 store).  The
+    checks run before any device work."""
+    from clipa_amd import ops
+    x = torch.zeros(16, 16, dtype=torch.bfloat16)
+    with pytest.raises(RuntimeError, match="want_colsum"):
+        ops.quantize_rows(x, want_rownorm=True)
+    with pytest.raises(RuntimeError, match="out_dtype"):
+        ops.gemm_tn(x, x, torch.float16)
+    with pytest.raises(RuntimeError, match="out_dtype"):
+        ops.gemm_tn_f8(x.view(torch.uint8), x.view(torch.uint8), out_dtype=torch.float16)
+
+
 def test_registry_and_factory():
     assert {"ViT-S-16", "ViT-B-16", "ViT-L-16", "ViT-H-14", "ViT-L-16-CL8-Syntax-GAP"} <= set(clipa_amd.list_models())
     L = clipa_amd.get_model_config("ViT-L-16")
