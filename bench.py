@@ -2,6 +2,7 @@
 """bench.py - image-text pairs/sec of the full CLIP training step on N MI355X of one node.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full   # + fp8 line, extra regions, CPU baseline (FULL_ONLY_STEPS)
     python bench.py --gpus N --steps K --warmup W          # N > 1 without a launcher: re-executes itself under torch.distributed.run
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -11,6 +12,11 @@ HBM) -> model forward -> global InfoNCE loss (local_loss + gather_with_grad, the
 backward -> DDP gradient all-reduce -> AdamW -> logit_scale clamp.  Default workload = BASELINE.json's headline
 configuration at its per-GPU shape: ViT-L/16 @ 224, text-77, bf16 compute, local batch 4096 (weak scaling:
 global batch 4096*N, i.e. 32768 at N=8).  Prints ONE JSON line (rank 0).
+
+A plain run does only what that line's headline figure needs: set-up (including the keep planner's trial steps), the warm-up,
+the timed steps, --dump-outputs and the line.  --full adds the measurements that cost runs of their own, reported next to
+`value` and never part of it: the same workload in fp8, the uninstrumented, host-fed, bit-exact-plan and unpadded-text
+regions, and the CPU baseline.
 """
 import argparse
 import json
@@ -302,7 +308,12 @@ def self_launch_argv(n_gpus, script_args, port=None):
             "--master-addr", "127.0.0.1", "--master-port", str(int(port)), os.path.abspath(__file__)] + list(script_args)
 
 
-def main():
+# Steps of the measurements the headline figure does not need, at their --full defaults: a plain run takes none of them
+# unless its command line asks for a count.
+FULL_ONLY_STEPS = {"fp8_line_steps": 3, "plain_steps": 3, "h2d_steps": 5, "exact_steps": 3, "unpad_steps": 3}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -324,11 +335,11 @@ def main():
                     help="plan whole tiers (medium, then light8 upgrades) instead of tensor by tensor (the round-4 default for bf16)")
     ap.add_argument("--no-light8", action="store_true",
                     help="keep bit-exact tensors only: no e4m3 pre-activation (per-tensor plan: the bf16 pre-activation ranks below "
-                         "qkv; --tier-plan: the bf16 'light' tier instead of 'light8').  The default run reports this plan's rate as "
+                         "qkv; --tier-plan: the bf16 'light' tier instead of 'light8').  --full reports this plan's rate as "
                          "`value_exact_tiers` next to `value`")
-    ap.add_argument("--exact-steps", type=int, default=3,
+    ap.add_argument("--exact-steps", type=int, default=None,
                     help="extra steps after the timed region under the keep plan restricted to bit-exact tensors (same budget, no e4m3 "
-                         "pre-activation): reported as `value_exact_tiers`, never part of `value` (0 = skip)")
+                         "pre-activation): reported as `value_exact_tiers`, never part of `value` (0 = skip; default 3 with --full, else 0)")
     ap.add_argument("--no-second-pass", action="store_true",
                     help="skip the second planning pass (spend only the budget derived from the all-recompute step's peak)")
     ap.add_argument("--second-pass-fraction", type=float, default=None,
@@ -338,11 +349,15 @@ def main():
                     help="run the TIMED region with the engine's unpad_text knob (causal text tower on the tokens up to each caption's "
                          "EOT only; identical features / loss / gradients).  Off by default: `value` is measured on the reference's "
                          "schedule (all 77 positions); the unpadded rate is reported next to it as `unpadded_text`")
-    ap.add_argument("--unpad-steps", type=int, default=3,
-                    help="extra steps after the timed region with unpad_text on (reported as `unpadded_text`, never part of `value`; 0 = skip)")
+    ap.add_argument("--unpad-steps", type=int, default=None,
+                    help="extra steps after the timed region with unpad_text on (reported as `unpadded_text`, never part of `value`; "
+                         "0 = skip; default 3 with --full, else 0)")
     ap.add_argument("--alloc-conf", default=None,
                     help="PyTorch caching-allocator settings applied before the first allocation, e.g. expandable_segments:True")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the fp8 line, the uninstrumented, host-fed, bit-exact-plan "
+                         "and unpadded-text regions (their --*-steps) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--shapes", action="store_true", help="also report time and TF/s per GEMM / attention shape (stderr)")
     ap.add_argument("--accum-freq", type=int, default=1,
                     help="the reference's --accum-freq (train.py:216-256): the local batch is processed as this many micro-batches "
@@ -353,25 +368,34 @@ def main():
                          "clipa_amd.zero.ShardedAdamW (gradient reduce-scatter, optimizer state / W, parameter all-gather; no DDP wrapper)")
     ap.add_argument("--exchange", default="reduce_scatter", choices=["reduce_scatter", "all_to_all"],
                     help="--optimizer sharded: RCCL reduce-scatter, or one-hop all-to-all over the xGMI mesh + local sum")
-    ap.add_argument("--h2d-steps", type=int, default=5,
+    ap.add_argument("--h2d-steps", type=int, default=None,
                     help="extra steps (after the timed region, not part of `value`) whose batches come from pinned host memory "
-                         "through the device input pipeline: reported as `h2d_inclusive` (0 = skip)")
-    ap.add_argument("--plain-steps", type=int, default=3,
+                         "through the device input pipeline: reported as `h2d_inclusive` (0 = skip; default 5 with --full, else 0)")
+    ap.add_argument("--plain-steps", type=int, default=None,
                     help="extra steps after the timed region WITHOUT the per-launch HIP-event instrumentation of clipa_amd.ops: "
-                         "reported as `uninstrumented_ms_per_step` next to `ms_per_step` (0 = skip)")
+                         "reported as `uninstrumented_ms_per_step` next to `ms_per_step` (0 = skip; default 3 with --full, else 0)")
     ap.add_argument("--cpu-sample", type=int, default=8, help="pairs per CPU-baseline step")
     ap.add_argument("--cpu-timeout", type=int, default=240)
-    ap.add_argument("--fp8-line-steps", type=int, default=3,
+    ap.add_argument("--fp8-line-steps", type=int, default=None,
                     help="one GPU, bf16 run: BEFORE this process touches the GPU, the same workload is measured in fp8 (BASELINE configs[3]'s "
                          "precision; create_model(precision='fp8')) by a child `bench.py --precision fp8` with this many timed steps and "
-                         "reported as `fp8_same_workload`, never part of `value` (0 = skip)")
+                         "reported as `fp8_same_workload`, never part of `value` (0 = skip; default 3 with --full, else 0)")
     ap.add_argument("--fp8-line-timeout", type=int, default=300)
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (loss, logit scale, features, sampled "
                          "parameters and gradients) as DIR/<name>.npy (rank 0)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    for name, steps in FULL_ONLY_STEPS.items():          # counts not given: their --full default, none on a plain run
+        if getattr(args, name) is None:
+            setattr(args, name, steps if args.full else 0)
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    return args
+
+
+def main():
+    args = parse_args()
 
     if (args.gpus > 1 or os.environ.get("CLIPA_BENCH_FORCE_DIST") == "1") and "WORLD_SIZE" not in os.environ:
         # no launcher around us: become one (same arguments, one rank per GPU); never returns.  (CLIPA_BENCH_FORCE_DIST=1: the
@@ -973,7 +997,7 @@ def main():
                 if "|" in k:
                     print(f"SHAPE {k:48s} n={v['launches'] // args.steps:4d}/step {v['ms'] / args.steps:8.2f} ms/step "
                           f"{v['work'] / max(v['ms'], 1e-9) / 1e9:7.1f} TF/s", file=sys.stderr)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu_baseline:
             # bounded: run in a child process with a wall-clock limit so the bench line is never held hostage
             import subprocess
             threads = usable_cores()

@@ -458,3 +458,21 @@ def test_bench_fp8_child_line_survives_a_failing_child():
         assert cmd[cmd.index(flag) + 1] == val, flag
     assert "--no-cpu-baseline" in cmd
     assert line["value"] is None and "no GPU visible" in line["error"]
+
+
+def test_bench_plain_run_measures_the_headline_only():
+    """`bench.py --gpus 1 --steps K --warmup W` does only what its headline figure needs: the fp8 line, the extra regions after
+    the timed one and the CPU baseline run under --full, at the counts they had before; a count given on the command line is
+    honoured with or without it."""
+    import bench
+    extra = ("fp8_line_steps", "plain_steps", "h2d_steps", "exact_steps", "unpad_steps")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert (plain.full, plain.cpu_baseline, plain.steps, plain.warmup) == (False, False, 20, 5)
+    assert all(getattr(plain, k) == 0 for k in extra)
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.cpu_baseline and (full.steps, full.warmup) == (20, 5)
+    assert {k: getattr(full, k) for k in extra} == \
+        {"fp8_line_steps": 3, "plain_steps": 3, "h2d_steps": 5, "exact_steps": 3, "unpad_steps": 3}
+    assert not bench.parse_args(["--full", "--no-cpu-baseline"]).cpu_baseline
+    assert bench.parse_args(["--plain-steps", "2"]).plain_steps == 2
+    assert bench.parse_args(["--full", "--h2d-steps", "0"]).h2d_steps == 0

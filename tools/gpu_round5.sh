@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 R="$PWD"
 STAGES="${*:-headline benchq}"
-BENCHQ="--steps 3 --warmup 1 --no-cpu-baseline --h2d-steps 0 --plain-steps 0"
+BENCHQ="--full --steps 3 --warmup 1 --no-cpu-baseline --h2d-steps 0 --plain-steps 0"
 for s in $STAGES; do
   case $s in
     alltests)
