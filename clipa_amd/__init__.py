@@ -3,7 +3,7 @@
 Public surface mirrors `open_clip` (clipa_torch/open_clip/__init__.py) for the ViT-CLIP hot path:
 create_model, create_model_and_transforms, create_loss, CLIP, ClipLoss, DistillClipLoss, convert_weights_to_lp,
 get_cast_dtype, list_models, add_model_config; and the trainer's validation (training/train.py: evaluate,
-get_clip_metrics).
+get_clip_metrics) and multi-caption image-text retrieval (`image_text_retrieval`, `evaluate_retrieval`).
 """
 from .configs import add_model_config, get_model_config, list_models
 from .factory import (create_loss, create_model, create_model_and_transforms, get_cast_dtype, load_checkpoint)
@@ -13,6 +13,7 @@ from .model import (CLIP, CLIPTextCfg, CLIPVisionCfg, OPENAI_DATASET_MEAN, OPENA
 
 from .data import DeviceAugment, DevicePrefetcher
 from .evaluate import evaluate, get_clip_metrics, metrics_from_ranks
+from .retrieval_eval import evaluate_retrieval, image_text_retrieval
 from .transform import AugmentationCfg, image_transform
 from .zero import ShardedAdamW
 

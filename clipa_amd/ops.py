@@ -1071,6 +1071,59 @@ def retrieval_ranks(img, txt, scale=None):
     return tuple(out[k, :N] for k in range(4))
 
 
+def retrieval_ranks_multi(img, txt, txt2img, scale=None):
+    """Multi-caption retrieval ranks (image_text_retrieval.py of the reference's evaluators) without the [Ni, Nt]
+    similarities: img f32 [Ni, E], txt f32 [Nt, E], txt2img integer [Nt] on the device (text t describes image c(t) in
+    [0, Ni)), v = s * img @ txt^T in fp32 with s = scale[0] read on the device (None = 1).  Returns int32 (i2t_gt, i2t_eq)
+    [Ni] and (t2i_gt, t2i_eq) [Nt] in the caller's text order: per image i the number of texts that beat / tie (not its
+    own) its best caption's score m_i, per text t the number of images that beat / tie (other than c(t)) v_{c(t), t}.
+    A captionless image has m_i = -inf, so i2t_gt = Nt.  Ties resolve in the positive's favour (gt), as retrieval_ranks.
+    The kernel is fastest with the captions of an image adjacent; other orders are stable-sorted by image here (a
+    temporary permuted copy of txt) and the per-text results scattered back, so the result does not depend on the order."""
+    _chk(img, f32, "img", 2)
+    _chk(txt, f32, "txt", 2)
+    if not torch.is_tensor(txt2img) or not txt2img.is_cuda or txt2img.dim() != 1 or txt2img.dtype.is_floating_point \
+            or txt2img.dtype.is_complex or txt2img.dtype == torch.bool:
+        raise RuntimeError("retrieval_ranks_multi: txt2img must be a 1-D integer GPU tensor")
+    if img.shape[1] != txt.shape[1] or txt2img.shape[0] != txt.shape[0]:
+        raise RuntimeError(f"retrieval_ranks_multi: img {tuple(img.shape)}, txt {tuple(txt.shape)} and txt2img "
+                           f"{tuple(txt2img.shape)} must be [Ni, E], [Nt, E] and [Nt]")
+    Ni, Nt = img.shape[0], txt.shape[0]
+    if Ni < 1 or Nt < 1:
+        raise RuntimeError(f"retrieval_ranks_multi: needs at least one image and one text (Ni = {Ni}, Nt = {Nt})")
+    c = txt2img.to(torch.int64)
+    lo, hi, unsorted = torch.stack([c.min(), c.max(), (c[1:] < c[:-1]).sum()]).tolist()      # one host sync
+    if lo < 0 or hi >= Ni:
+        raise RuntimeError(f"retrieval_ranks_multi: txt2img values must lie in [0, {Ni}); got [{lo}, {hi}]")
+    order = None
+    if unsorted:
+        order = torch.argsort(c, stable=True)
+        txt, c = txt.index_select(0, order), c[order]
+    c = c.to(torch.int32)                                  # a fresh, 16-byte aligned buffer
+    img, lda = _rowmajor(img)
+    txt, ldb = _rowmajor(txt)
+    if lda % 4 or img.data_ptr() % 16:
+        img, lda = _pad_cols4(img)
+    if ldb % 4 or txt.data_ptr() % 16:
+        txt, ldb = _pad_cols4(txt)
+    E = img.shape[1]
+    if scale is not None:
+        _chk(scale, f32, "scale")
+        scale = scale.reshape(1).contiguous()
+    dev = img.device
+    wsb = lib.query("clipa_retrieval_ranks_multi_workspace", Ni, Nt)
+    ws = torch.empty(max(wsb, 16) // 4, device=dev, dtype=f32)
+    oi = torch.empty((2, (Ni + 3) // 4 * 4), device=dev, dtype=torch.int32)       # rows 16-byte aligned
+    ot = torch.empty((2, (Nt + 3) // 4 * 4), device=dev, dtype=torch.int32)
+    with _Timed("retrieval_ranks_multi", 2.0 * Ni * Nt * E):
+        lib.call("clipa_retrieval_ranks_multi", _p(img), _p(txt), _p(c), Ni, Nt, E, lda, ldb, _p(scale), _p(oi[0]),
+                 _p(oi[1]), _p(ot[0]), _p(ot[1]), _p(ws), wsb, _stream())
+    t2i_gt, t2i_eq = ot[0, :Nt], ot[1, :Nt]
+    if order is not None:
+        t2i_gt, t2i_eq = (torch.empty_like(t).index_copy_(0, order, t) for t in (t2i_gt, t2i_eq))
+    return oi[0, :Ni], oi[1, :Ni], t2i_gt, t2i_eq
+
+
 def _pad_cols4(x):
     """[N, E] -> (a [N, E] view of a fresh [N, E rounded up to 4] buffer, its row stride): the kernel wants 16-byte
     aligned rows."""

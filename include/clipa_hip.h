@@ -311,6 +311,23 @@ int64_t clipa_retrieval_ranks_workspace(int64_t N);
 int clipa_retrieval_ranks(const float* A, const float* B, int64_t N, int64_t E, int64_t lda, int64_t ldb,
                           const float* scale, int32_t* i2t_gt, int32_t* i2t_eq, int32_t* t2i_gt, int32_t* t2i_eq,
                           void* workspace, int64_t workspace_bytes, void* stream);
+/* Multi-caption image-text retrieval ranks (clipa_jax/evaluators/proj/image_text/image_text_retrieval.py: COCO, Flickr30k)
+ * without the [Ni, Nt] similarity matrix.  A (image features) fp32 [Ni, E], B (text features) fp32 [Nt, E], leading
+ * dimensions lda, ldb (>= E, multiples of 4); txt2img int32 [Nt] in DEVICE memory, text t describing image c(t) in
+ * [0, Ni) (callers validate it; the kernels never index with it); s from DEVICE memory (NULL = 1).  With
+ * v_it = fl(s * (A_i . B_t)), every x_it computed by the same fp32 arithmetic as clipa_retrieval_ranks:
+ *   p_t = v_{c(t), t}   m_i = max over {t : c(t) = i} of p_t   (-inf when image i has no caption)
+ *   t2i_gt[t] = #{i : v_it > p_t}   t2i_eq[t] = #{i != c(t) : v_it == p_t}          (text -> image)
+ *   i2t_gt[i] = #{t : v_it > m_i}   i2t_eq[i] = #{t : c(t) != i, v_it == m_i}       (image -> text)
+ * i2t_gt is the 0-based position of image i's best caption (Nt for a captionless image), t2i_gt that of text t's image;
+ * tie rule as clipa_retrieval_ranks.  Any c is correct; c non-decreasing (the captions of an image adjacent) makes the
+ * positives pass touch about Ti + Tt 128 x 128 tiles instead of up to Ti * Tt.  All pointers 16-byte aligned (scale 4);
+ * the count arrays need no clearing.  Workspace: clipa_retrieval_ranks_multi_workspace(Ni, Nt) bytes.  Memory is
+ * O(Ni + Nt). */
+int64_t clipa_retrieval_ranks_multi_workspace(int64_t Ni, int64_t Nt);
+int clipa_retrieval_ranks_multi(const float* A, const float* B, const int32_t* txt2img, int64_t Ni, int64_t Nt, int64_t E,
+                                int64_t lda, int64_t ldb, const float* scale, int32_t* i2t_gt, int32_t* i2t_eq,
+                                int32_t* t2i_gt, int32_t* t2i_eq, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* AdamW over one flat tensor (training/main.py:318-326 torch.optim.AdamW + train.py:285-286 clamp is
  * done by the caller): p -= lr*(m_hat/(sqrt(v_hat)+eps) + wd*p). param/grad bf16 or f32; m, v f32. */
