@@ -18,7 +18,6 @@
 // ds_read_b64_tr_b16.  The backward pass is two sweeps (query-major for dQ, key-major for dK/dV)
 // that recompute the probabilities from per-row (max, 1/sum) statistics kept in LDS.
 #include "common.h"
-#include <mutex>
 #include "clipa_hip.h"
 #include "attention_common.h"
 #include "internal_hooks.h"
@@ -609,24 +608,15 @@ __global__ __launch_bounds__(256, HD<DH>::WGS) void attn_bwd_long_kernel(AttnArg
   }
 }
 
-constexpr int ATTN_MAX_DEVICES = 64;
-
 template <int NKT, int DH, bool CAUSAL>
 int launch_fwd_c(const AttnArgs& a, hipStream_t st) {
   constexpr int HPW = WGHeads<NKT>::HPW;
   const int lds = HPW * 2 * NKT * 32 * HD<DH>::RB + (fwd_stages<NKT, DH>() ? attn_waves<NKT, DH>() * Stg<DH>::BYTES : 0);
-  // the LDS opt-in is a per-device function attribute: once per (kernel instantiation, device), thread-safe (the
-  // forward runs on the Python main thread, the backward on autograd's worker thread)
-  static std::once_flag once[ATTN_MAX_DEVICES];
-  static int rc_dev[ATTN_MAX_DEVICES];
+  // one opt-in per kernel instantiation: the LDS size differs between them
+  static clipa_gemm::LdsOptIn optin;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= ATTN_MAX_DEVICES) { clipa_set_error("attn_fwd: bad device"); return CLIPA_ERR_LAUNCH; }
-  std::call_once(once[dev], [&]() {
-    const hipError_t e = hipFuncSetAttribute((const void*)attn_fwd_kernel<NKT, DH, CAUSAL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    rc_dev[dev] = 0;
-    if (e != hipSuccess) { clipa_set_error("attn_fwd attr: %s", hipGetErrorString(e)); rc_dev[dev] = CLIPA_ERR_LAUNCH; }
-  });
-  if (rc_dev[dev]) return rc_dev[dev];
+  if (int rc = clipa_gemm::current_device(&dev)) return rc;
+  if (int rc = optin.ensure(dev, {(const void*)attn_fwd_kernel<NKT, DH, CAUSAL>}, lds, "attn_fwd")) return rc;
   hipLaunchKernelGGL((attn_fwd_kernel<NKT, DH, CAUSAL>), dim3((unsigned)(((long)a.B * a.H + HPW - 1) / HPW)), dim3(64 * attn_waves<NKT, DH>()), lds, st, a);
   return clipa_check_launch("attn_fwd");
 }
@@ -638,18 +628,11 @@ template <int NKT, int DH, bool CAUSAL>
 int launch_bwd_c(const AttnArgs& a, hipStream_t st) {
   constexpr int HPW = WGHeads<NKT>::HPW;
   const int lds = HPW * (2 * NKT * 32 * HD<DH>::RB + 3 * NKT * 32 * 4) + (bwd_stages<NKT, DH>() ? attn_waves<NKT, DH>() * Stg<DH>::BYTES : 0);
-  // the LDS opt-in is a per-device function attribute: once per (kernel instantiation, device), thread-safe (the
-  // forward runs on the Python main thread, the backward on autograd's worker thread)
-  static std::once_flag once[ATTN_MAX_DEVICES];
-  static int rc_dev[ATTN_MAX_DEVICES];
+  // one opt-in per kernel instantiation: the LDS size differs between them
+  static clipa_gemm::LdsOptIn optin;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= ATTN_MAX_DEVICES) { clipa_set_error("attn_bwd: bad device"); return CLIPA_ERR_LAUNCH; }
-  std::call_once(once[dev], [&]() {
-    const hipError_t e = hipFuncSetAttribute((const void*)attn_bwd_kernel<NKT, DH, CAUSAL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    rc_dev[dev] = 0;
-    if (e != hipSuccess) { clipa_set_error("attn_bwd attr: %s", hipGetErrorString(e)); rc_dev[dev] = CLIPA_ERR_LAUNCH; }
-  });
-  if (rc_dev[dev]) return rc_dev[dev];
+  if (int rc = clipa_gemm::current_device(&dev)) return rc;
+  if (int rc = optin.ensure(dev, {(const void*)attn_bwd_kernel<NKT, DH, CAUSAL>}, lds, "attn_bwd")) return rc;
   hipLaunchKernelGGL((attn_bwd_kernel<NKT, DH, CAUSAL>), dim3((unsigned)(((long)a.B * a.H + HPW - 1) / HPW)), dim3(64 * attn_waves<NKT, DH>()), lds, st, a);
   return clipa_check_launch("attn_bwd");
 }
@@ -662,16 +645,10 @@ template <int DH, bool CAUSAL, bool BWD>
 int launch_long(const AttnArgs& a, hipStream_t st) {
   const int lds = 2 * LONG_CT * 32 * HD<DH>::RB + (BWD ? 3 * LONG_LMAX * 4 : 0);
   const void* fn = BWD ? (const void*)attn_bwd_long_kernel<DH, CAUSAL> : (const void*)attn_fwd_long_kernel<DH, CAUSAL>;
-  static std::once_flag once[ATTN_MAX_DEVICES];
-  static int rc_dev[ATTN_MAX_DEVICES];
+  static clipa_gemm::LdsOptIn optin;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= ATTN_MAX_DEVICES) { clipa_set_error("attention: bad device"); return CLIPA_ERR_LAUNCH; }
-  std::call_once(once[dev], [&]() {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    rc_dev[dev] = 0;
-    if (e != hipSuccess) { clipa_set_error("attention (long) attr: %s", hipGetErrorString(e)); rc_dev[dev] = CLIPA_ERR_LAUNCH; }
-  });
-  if (rc_dev[dev]) return rc_dev[dev];
+  if (int rc = clipa_gemm::current_device(&dev)) return rc;
+  if (int rc = optin.ensure(dev, {fn}, lds, "attention (long)")) return rc;
   const dim3 grid((unsigned)((long)a.B * a.H));
   if (BWD) hipLaunchKernelGGL((attn_bwd_long_kernel<DH, CAUSAL>), grid, dim3(256), lds, st, a);
   else hipLaunchKernelGGL((attn_fwd_long_kernel<DH, CAUSAL>), grid, dim3(256), lds, st, a);

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
+#include <mutex>
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;   // 8 bf16 = 4 VGPRs (MFMA A/B operand)
 typedef __attribute__((ext_vector_type(4))) short bf16x4;   // 4 bf16 = 2 VGPRs
@@ -20,6 +22,21 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 void clipa_set_error(const char* fmt, ...);
 int clipa_check_launch(const char* what);
+
+// Per-device launch state (host; defined in gemm_nt.hip).
+namespace clipa_gemm {
+constexpr int MAX_DEVICES = 64;
+int current_device(int* dev);             // hipGetDevice with error reporting; *dev in [0, MAX_DEVICES)
+// Opt-in of a set of kernels to more than 64 KiB of dynamic LDS.  The limit is a per-device function attribute: set once per
+// (kernel set, device), thread-safe (the forward runs on the Python main thread, the backward on autograd's worker
+// thread), the error remembered for every later call.  One static object per kernel set; a function-local static of a
+// launcher template is one per instantiation.
+struct LdsOptIn {
+  std::once_flag once[MAX_DEVICES];
+  int rc[MAX_DEVICES];
+  int ensure(int dev, std::initializer_list<const void*> kernels, int bytes, const char* what);
+};
+}  // namespace clipa_gemm
 
 // ---- bf16 <-> f32 -------------------------------------------------------------------------
 __device__ __forceinline__ float bf2f(unsigned short h) {

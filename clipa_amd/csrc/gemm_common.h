@@ -4,7 +4,6 @@
 #include "common.h"
 #include "clipa_hip.h"
 #include <atomic>
-#include <mutex>
 
 namespace clipa_gemm {
 
@@ -335,10 +334,9 @@ __device__ __forceinline__ void lds_read4_f1(float (&v)[4], const char* base) { 
 #define RING_WAIT_ALL() asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #define RING_WAIT_AFTER_EPILOGUE(NSTORES) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(NSTORES) : "memory")
 
-// Per-device launch state: LDS opt-in attributes are set once per device (std::call_once), the CU count is read
+// Per-device launch state: LDS opt-in attributes are set once per device (LdsOptIn, common.h), the CU count is read
 // from the device the call runs on.  No process-wide mutable state besides the experiment knobs (atomics).
 int gemm_num_cu(int dev);                 // multiProcessorCount of `dev`, cached
-int current_device(int* dev);             // hipGetDevice with error reporting
 extern std::atomic<int> g_nt_variant;     // clipa_internal_debug_set: gemm_nt kernel selection (0 = per-shape default)
 extern std::atomic<int> g_abl;            // clipa_internal_debug_set: experiment flags
 extern std::atomic<int> g_last_gemm;      // clipa_internal_last_gemm: 1 gemm_nt2, 2 gemm_nta, 3 gemm_tn2, 4 gemm_tn3, 5 gemm_tna
@@ -352,8 +350,6 @@ inline void note_gemm(int family, int extra = 0) {
   g_gemm_count[family].fetch_add(1, std::memory_order_relaxed);
   if (extra) g_gemm_count[extra].fetch_add(1, std::memory_order_relaxed);
 }
-
-constexpr int MAX_DEVICES = 64;
 
 // gemm_nta.hip: the four-wave / hand-scheduled kernel for whole-tile bf16 shapes (clipa_gemm_nt dispatches to it)
 constexpr int NTA_DEFAULT_SCHEDULE = 4;   // profiles/r03_gemm_nta_schedules_0_7_mainloop_ablation.jsonl

@@ -198,24 +198,14 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_f8_kernel(F8Args p) {
   }
 }
 
-std::once_flag g_f8_once[MAX_DEVICES];
-int g_f8_rc[MAX_DEVICES];
-
+LdsOptIn g_f8_lds;
 int ensure_f8_attrs(int dev) {
-  std::call_once(g_f8_once[dev], [dev]() {
-    int rc = 0;
 #define F8_KS(E, P2) (const void*)gemm_nt_f8_kernel<0, 0, E, P2>, (const void*)gemm_nt_f8_kernel<1, 0, E, P2>, \
                      (const void*)gemm_nt_f8_kernel<0, 1, E, P2>, (const void*)gemm_nt_f8_kernel<1, 1, E, P2>
-    const void* ks[20] = {F8_KS(CLIPA_EPI_NONE, false), F8_KS(CLIPA_EPI_ACT, false), F8_KS(CLIPA_EPI_ACT, true),
-                          F8_KS(CLIPA_EPI_ADD, false), F8_KS(CLIPA_EPI_DACT, false)};
+  return g_f8_lds.ensure(dev, {F8_KS(CLIPA_EPI_NONE, false), F8_KS(CLIPA_EPI_ACT, false), F8_KS(CLIPA_EPI_ACT, true),
+                               F8_KS(CLIPA_EPI_ADD, false), F8_KS(CLIPA_EPI_DACT, false)},
+                         F8_LDS_BYTES, "gemm_nt_f8");
 #undef F8_KS
-    for (int i = 0; i < 20; ++i) {
-      const hipError_t e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, F8_LDS_BYTES);
-      if (e != hipSuccess) { clipa_set_error("hipFuncSetAttribute(gemm_nt_f8): %s", hipGetErrorString(e)); rc = CLIPA_ERR_LAUNCH; }
-    }
-    g_f8_rc[dev] = rc;
-  });
-  return g_f8_rc[dev];
 }
 
 }  // namespace

@@ -284,25 +284,15 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt2_kernel(NTArgs p) {
 }
 
 
-std::once_flag g_nt_once[MAX_DEVICES];
-int g_nt_rc[MAX_DEVICES];
-
+LdsOptIn g_nt_lds;
 int ensure_nt_attrs(int dev) {
-  std::call_once(g_nt_once[dev], [dev]() {
-    int rc = 0;
-    const void* v2[6] = {(const void*)gemm_nt2_kernel<true, false>,
-                         (const void*)gemm_nt2_kernel<false, true, true, CLIPA_EPI_NONE, false>,
-                         (const void*)gemm_nt2_kernel<false, true, true, CLIPA_EPI_ACT, false>,
-                         (const void*)gemm_nt2_kernel<false, true, true, CLIPA_EPI_ACT, true>,
-                         (const void*)gemm_nt2_kernel<false, true, true, CLIPA_EPI_ADD, false>,
-                         (const void*)gemm_nt2_kernel<false, true, true, CLIPA_EPI_DACT, false>};
-    for (int i = 0; i < 6; ++i) {
-      const hipError_t e = hipFuncSetAttribute(v2[i], hipFuncAttributeMaxDynamicSharedMemorySize, LDS2_BYTES);
-      if (e != hipSuccess) { clipa_set_error("hipFuncSetAttribute(gemm_nt2): %s", hipGetErrorString(e)); rc = CLIPA_ERR_LAUNCH; }
-    }
-    g_nt_rc[dev] = rc;
-  });
-  return g_nt_rc[dev];
+  return g_nt_lds.ensure(dev, {(const void*)gemm_nt2_kernel<true, false>,
+                               (const void*)gemm_nt2_kernel<false, true, true, CLIPA_EPI_NONE, false>,
+                               (const void*)gemm_nt2_kernel<false, true, true, CLIPA_EPI_ACT, false>,
+                               (const void*)gemm_nt2_kernel<false, true, true, CLIPA_EPI_ACT, true>,
+                               (const void*)gemm_nt2_kernel<false, true, true, CLIPA_EPI_ADD, false>,
+                               (const void*)gemm_nt2_kernel<false, true, true, CLIPA_EPI_DACT, false>},
+                         LDS2_BYTES, "gemm_nt2");
 }
 
 }  // namespace
@@ -317,6 +307,17 @@ int current_device(int* dev) {
   if (e != hipSuccess) { clipa_set_error("hipGetDevice: %s", hipGetErrorString(e)); return CLIPA_ERR_LAUNCH; }
   if (*dev < 0 || *dev >= MAX_DEVICES) { clipa_set_error("device ordinal %d out of range", *dev); return CLIPA_ERR_ARG; }
   return 0;
+}
+
+int LdsOptIn::ensure(int dev, std::initializer_list<const void*> kernels, int bytes, const char* what) {
+  std::call_once(once[dev], [&]() {
+    rc[dev] = 0;
+    for (const void* k : kernels) {
+      const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+      if (e != hipSuccess) { clipa_set_error("hipFuncSetAttribute(%s): %s", what, hipGetErrorString(e)); rc[dev] = CLIPA_ERR_LAUNCH; }
+    }
+  });
+  return rc[dev];
 }
 
 int gemm_num_cu(int dev) {

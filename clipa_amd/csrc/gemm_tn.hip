@@ -376,18 +376,9 @@ __global__ void reduce_slabs_kernel(const float* __restrict__ slabs, void* __res
   }
 }
 
-std::once_flag g_tn_once[MAX_DEVICES];
-int g_tn_rc[MAX_DEVICES];
+LdsOptIn g_tn_lds;
 int ensure_tn_attrs(int dev) {
-  std::call_once(g_tn_once[dev], [dev]() {
-    g_tn_rc[dev] = 0;
-    const void* ks[2] = {(const void*)gemm_tn3_kernel, (const void*)gemm_tn2_kernel};
-    for (int i = 0; i < 2; ++i) {
-      const hipError_t e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES);
-      if (e != hipSuccess) { clipa_set_error("hipFuncSetAttribute(gemm_tn): %s", hipGetErrorString(e)); g_tn_rc[dev] = CLIPA_ERR_LAUNCH; }
-    }
-  });
-  return g_tn_rc[dev];
+  return g_tn_lds.ensure(dev, {(const void*)gemm_tn3_kernel, (const void*)gemm_tn2_kernel}, 2 * STAGE_BYTES, "gemm_tn");
 }
 
 }  // namespace

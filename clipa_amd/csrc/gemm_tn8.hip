@@ -208,8 +208,7 @@ __global__ void reduce_slabs_alpha_kernel(const float* __restrict__ slabs, void*
   }
 }
 
-std::once_flag g_tn8_once[MAX_DEVICES];
-int g_tn8_rc[MAX_DEVICES];
+LdsOptIn g_tn8_lds;
 
 // schedule 2 (four column-major tail rows: one transposing read per MFMA slot throughout) wins 14 of the 16 production shapes by
 // 1-5 % over schedule 1 (profiles/r06_gemm_tn8_schedules_and_work_orders.jsonl)
@@ -255,16 +254,7 @@ TN8Plan tn8_plan(long M, long R, long C, int num_cu) {
   return pl;
 }
 
-template <int FMT_P>
-int tn8_set_attrs() {
-  int rc = 0;
-  const void* k[3] = {(const void*)gemm_tn8_kernel<0, FMT_P>, (const void*)gemm_tn8_kernel<1, FMT_P>, (const void*)gemm_tn8_kernel<2, FMT_P>};
-  for (int i = 0; i < 3; ++i) {
-    const hipError_t e = hipFuncSetAttribute(k[i], hipFuncAttributeMaxDynamicSharedMemorySize, TN8_LDS);
-    if (e != hipSuccess) { clipa_set_error("hipFuncSetAttribute(gemm_tn8): %s", hipGetErrorString(e)); rc = CLIPA_ERR_LAUNCH; }
-  }
-  return rc;
-}
+#define TN8_KS(F) (const void*)gemm_tn8_kernel<0, F>, (const void*)gemm_tn8_kernel<1, F>, (const void*)gemm_tn8_kernel<2, F>
 
 template <int FMT_P>
 void tn8_launch_fast(const TN8Args& a, dim3 grid, int sched, hipStream_t st) {
@@ -309,8 +299,7 @@ extern "C" int clipa_gemm_tn_f8(const void* P8, const void* Q8, void* out, int64
   hipStream_t st = (hipStream_t)stream;
   if (pl.S_fast > 0) {
     if (pl.slice_rows * ldp >= (1L << 32) - (1 << 24) || pl.slice_rows * ldq >= (1L << 32) - (1 << 24)) { clipa_set_error("gemm_tn_f8: slice too large for 32-bit buffer offsets"); return CLIPA_ERR_ARG; }
-    std::call_once(g_tn8_once[dev], [dev]() { g_tn8_rc[dev] = tn8_set_attrs<0>() | tn8_set_attrs<1>(); });
-    if (g_tn8_rc[dev]) return g_tn8_rc[dev];
+    if (int rc = g_tn8_lds.ensure(dev, {TN8_KS(0), TN8_KS(1)}, TN8_LDS, "gemm_tn8")) return rc;
     TN8Args a;
     a.P = (const char*)P8; a.Q = (const char*)Q8; a.O = (float*)workspace;
     a.M = (int)pl.fast_rows; a.R = (int)R; a.C = (int)C; a.ldp = ldp; a.ldq = ldq; a.ldo = C;

@@ -141,8 +141,7 @@ __global__ __launch_bounds__(TNA_THREADS) void gemm_tna_kernel(TNArgs p) {
   }
 }
 
-std::once_flag g_tna_once[MAX_DEVICES];
-int g_tna_rc[MAX_DEVICES];
+LdsOptIn g_tna_lds;
 
 }  // namespace
 
@@ -154,15 +153,7 @@ bool tna_eligible(const TNArgs& a) {
 }
 
 int tna_launch(const TNArgs& a, int dev, dim3 grid, int sched, hipStream_t st) {
-  std::call_once(g_tna_once[dev], [dev]() {
-    g_tna_rc[dev] = 0;
-    const void* ks[2] = {(const void*)gemm_tna_kernel<0>, (const void*)gemm_tna_kernel<1>};
-    for (int i = 0; i < 2; ++i) {
-      const hipError_t e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, TNA_LDS);
-      if (e != hipSuccess) { clipa_set_error("hipFuncSetAttribute(gemm_tna): %s", hipGetErrorString(e)); g_tna_rc[dev] = CLIPA_ERR_LAUNCH; }
-    }
-  });
-  if (g_tna_rc[dev]) return g_tna_rc[dev];
+  if (int rc = g_tna_lds.ensure(dev, {(const void*)gemm_tna_kernel<0>, (const void*)gemm_tna_kernel<1>}, TNA_LDS, "gemm_tna")) return rc;
   note_gemm(5);
   if (sched == 1) hipLaunchKernelGGL(gemm_tna_kernel<1>, grid, dim3(TNA_THREADS), TNA_LDS, st, a);
   else hipLaunchKernelGGL(gemm_tna_kernel<0>, grid, dim3(TNA_THREADS), TNA_LDS, st, a);

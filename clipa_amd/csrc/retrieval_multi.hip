@@ -7,103 +7,20 @@
 // i2t_gt is the 0-based position of image i's best caption (its other captions cannot beat m_i), t2i_gt that of text
 // t's image; ties resolve in the positive's favour, as in retrieval.hip.
 //
-// Arithmetic: rank_tile below, the main loop of retrieval.hip's kernel kept instruction for instruction in the same k order
-// (one ascending-k fp32 MFMA chain per output, no split-K; tests/test_retrieval_multi_gpu.py checks the two agree bit for
-// bit), so every x_it - the positives included - comes out of the same code whichever launch or tile computes it.  Three launches:
+// Arithmetic: rank_tile (rank_tile.h), the main loop retrieval.hip's kernel runs too (one ascending-k fp32 MFMA chain per
+// output, no split-K; tests/test_retrieval_multi_gpu.py checks the two agree bit for bit), so every x_it - the positives
+// included - comes out of the same code whichever launch or tile computes it.  Three launches:
 //   init: counts = 0, p_t = NaN, m_i = key(-inf);
 //   POS:  one workgroup per 128-text tile, over the image tiles [min c, max c] of its texts (tiles that hold none of their
 //         images skipped): writes p_t and takes m_i by an integer atomicMax on an order-preserving key of the float.
 //         Sorted c (the captions of an image adjacent) makes this about Ti + Tt tiles;
 //   count: every Ti x Tt tile; the epilogue counts against m_i (rows) and p_t (columns), c of the tile's columns gives the
-//         eq exclusions, reduces as retrieval.hip does and adds one int per row and per column of the tile atomically.
+//         eq exclusions (rank_count, rank_tile.h, shared with retrieval.hip) and adds one int per row and per column of the tile atomically.
 // Memory: O(Ni + Nt) (the workspace is p_t and the keys of m_i).
-#include "gemm_common.h"
+#include "rank_tile.h"
 
 namespace clipa_gemm {
 namespace {
-
-constexpr int RT = 128;                       // output tile (rows of A and of B)
-constexpr int RK = 32;                        // k per stage
-constexpr int RTHREADS = 256;
-constexpr int R_IMG = RT * RK * 4;            // one operand image: 16 KiB
-constexpr int R_STAGE = 2 * R_IMG;
-
-// 8-byte slot swizzle of image row r: a bijection of 0..15 over any 16 consecutive rows that also differs between r and r + 16
-__device__ __forceinline__ int swz(int r) { return (r & 15) ^ ((r >> 4) & 1); }
-
-// acc[mi][ni] = the 32 x 32 block (mi, ni) of this wave's 64 x 64 quarter of the 128 x 128 tile of A rows (rsA) times B
-// rows (rsB), rows past a resource's range and k >= E reading 0.  Uses the first 2 * R_STAGE bytes of smem; the caller
-// synchronises before reusing them.
-// D fragment: lane holds column j = wn*64 + ni*32 + L and rows i = wm*64 + mi*32 + (r&3) + 8*(r>>2) + 4*hi of the tile.
-__device__ __forceinline__ void rank_tile(char* smem, __amdgpu_buffer_rsrc_t rsA, __amdgpu_buffer_rsrc_t rsB, long lda,
-                                          long ldb, int E, f32x16 (&acc)[2][2]) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int L = lane & 31, hi = lane >> 5;
-  const int wm = wave >> 1, wn = wave & 1;   // wave tile: 64 (i) x 64 (j)
-
-  // DMA piece pc (256 B = two rows of the image) = 16 j-steps x 4 waves; lane -> row 2 pc + hi, dword L of the row:
-  // 8-byte slot L / 2 holds pair (slot ^ swz(row)) = (q, h), element L & 1 is k = 4q + h + 2 (L & 1).
-  int kel[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int pr = (L >> 1) ^ swz(8 * j + 2 * wave + hi);
-    kel[j] = 4 * (pr >> 1) + (pr & 1) + 2 * (L & 1);
-  }
-  const unsigned rowA0 = (unsigned)((2 * wave + hi) * lda * 4), rowB0 = (unsigned)((2 * wave + hi) * ldb * 4);
-  const unsigned stepA = (unsigned)(8 * lda * 4), stepB = (unsigned)(8 * ldb * 4);
-
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-
-  auto stage = [&](int buf, int k0) {
-    char* sA = smem + buf * R_STAGE;
-    char* sB = sA + R_IMG;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const int pc = 4 * j + wave;
-      const int k = k0 + kel[j & 3];
-      const unsigned oob = k >= E ? 0x80000000u : 0u;   // ragged E: the buffer range check returns 0
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, LDS_PTR(sA + pc * 256), 4, (rowA0 + j * stepA + k * 4) | oob, 0, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, LDS_PTR(sB + pc * 256), 4, (rowB0 + j * stepB + k * 4) | oob, 0, 0, 0);
-    }
-  };
-
-  const int sw = swz(L);                      // fragment rows start at multiples of 32
-  const int rowoffA = (wm * 64 + L) * 128;
-  const int rowoffB = (wn * 64 + L) * 128;
-  const int nkt = (E + RK - 1) / RK;
-  stage(0, 0);
-  for (int kt = 0; kt < nkt; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (kt + 1 < nkt) stage((kt + 1) & 1, (kt + 1) * RK);
-    const char* sA = smem + (kt & 1) * R_STAGE;
-    const char* sB = sA + R_IMG;
-#pragma unroll
-    for (int q = 0; q < RK / 4; ++q) {
-      const int off = ((2 * q + hi) ^ sw) * 8;
-      f32x2 fa[2], fb[2];
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) fa[mi] = *(const f32x2*)(sA + rowoffA + mi * 32 * 128 + off);
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) fb[ni] = *(const f32x2*)(sB + rowoffB + ni * 32 * 128 + off);
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[mi].x, fb[ni].x, acc[mi][ni], 0, 0, 0);
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[mi].y, fb[ni].y, acc[mi][ni], 0, 0, 0);
-    }
-  }
-}
 
 struct MultiArgs {
   const char* A; const char* B; const int* c;
@@ -198,85 +115,10 @@ __global__ __launch_bounds__(RTHREADS, 2) void retrieval_multi_kernel(MultiArgs 
   }
   rank_tile(smem, rsA, rsB, p.lda, p.ldb, p.E, acc);
 
-  __syncthreads();                            // the ring is dead: reuse its first bytes
-  float* dpl = (float*)smem;                  // [256]: positives of the tile's rows, then of its columns
-  int* rowp = (int*)(smem + 1024);            // [2 wn][128]  packed gt | eq << 16 per row
-  int* colp = rowp + 2 * RT;                  // [2 wm][128]  per column
-  dpl[tid] = dpos;
-  __syncthreads();
-
-  float dcol[2];
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) dcol[ni] = dpl[RT + wn * 64 + ni * 32 + L];
-  int rc[32];                                 // per (mi, r): this lane's packed row counts over its two columns
-  int cc[2] = {0, 0};                         // per ni: packed column counts over this lane's 32 rows
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int il = wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-      const float drow = dpl[il];
-      int c = 0;
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        const int jl = wn * 64 + ni * 32 + L;
-        const float v = s * acc[mi][ni][r];
-        const bool ok = jl < rowsB && il < rowsA;
-        const bool other = cj[ni] != m0 + il;  // eq counts entries that are not the text's own image
-        c += ok ? (int)(v > drow) + ((int)(other && v == drow) << 16) : 0;
-        cc[ni] += ok ? (int)(v > dcol[ni]) + ((int)(other && v == dcol[ni]) << 16) : 0;
-      }
-      rc[mi * 16 + r] = c;
-    }
-  // rows: sum over the 32 lanes of each half; recursive halving leaves lane L with the total of value index L
-#pragma unroll
-  for (int b = 16; b >= 1; b >>= 1) {
-    const bool up = (L & b) != 0;
-#pragma unroll
-    for (int c = 0; c < b; ++c) {
-      const int send = up ? rc[c] : rc[c + b];
-      const int keep = up ? rc[c + b] : rc[c];
-      rc[c] = keep + __shfl_xor(send, b, 64);
-    }
-  }
-  {
-    const int r = L & 15;
-    rowp[wn * RT + wm * 64 + (L >> 4) * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi] = rc[0];
-  }
-  // columns: add the other lane half
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni) cc[ni] += __shfl_xor(cc[ni], 32, 64);
-  colp[wm * RT + wn * 64 + hi * 32 + L] = hi ? cc[1] : cc[0];
-  __syncthreads();
-  if (tid < RT) {
-    const int v = rowp[tid] + rowp[RT + tid];
-    if (tid < rowsA) {
-      if (v & 0xffff) atomicAdd(p.i2t_gt + m0 + tid, v & 0xffff);
-      if (v >> 16) atomicAdd(p.i2t_eq + m0 + tid, v >> 16);
-    }
-  } else {
-    const int t = tid - RT;
-    const int v = colp[t] + colp[RT + t];
-    if (t < rowsB) {
-      if (v & 0xffff) atomicAdd(p.t2i_gt + n0 + t, v & 0xffff);
-      if (v >> 16) atomicAdd(p.t2i_eq + n0 + t, v >> 16);
-    }
-  }
+  rank_count(smem, m0, n0, rowsA, rowsB, dpos, s, cj, acc, p.i2t_gt, p.i2t_eq, p.t2i_gt, p.t2i_eq);
 }
 
-std::once_flag g_rkm_once[MAX_DEVICES];
-int g_rkm_rc[MAX_DEVICES];
-int ensure_rkm_attrs(int dev) {
-  std::call_once(g_rkm_once[dev], [dev]() {
-    g_rkm_rc[dev] = 0;
-    const void* ks[2] = {(const void*)retrieval_multi_kernel<true>, (const void*)retrieval_multi_kernel<false>};
-    for (int i = 0; i < 2; ++i) {
-      const hipError_t e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, 2 * R_STAGE);
-      if (e != hipSuccess) { clipa_set_error("hipFuncSetAttribute(retrieval_multi): %s", hipGetErrorString(e)); g_rkm_rc[dev] = CLIPA_ERR_LAUNCH; }
-    }
-  });
-  return g_rkm_rc[dev];
-}
+LdsOptIn g_rkm_lds;
 
 }  // namespace
 }  // namespace clipa_gemm
@@ -297,24 +139,13 @@ extern "C" int clipa_retrieval_ranks_multi(const float* A, const float* B, const
     clipa_set_error("retrieval_ranks_multi: Ni = %ld, Nt = %ld and E = %ld must be >= 1", (long)Ni, (long)Nt, (long)E);
     return CLIPA_ERR_ARG;
   }
-  if (lda < E || ldb < E || lda % 4 != 0 || ldb % 4 != 0) {
-    clipa_set_error("retrieval_ranks_multi: lda = %ld and ldb = %ld must be >= E = %ld and multiples of 4", (long)lda, (long)ldb, (long)E);
-    return CLIPA_ERR_ARG;
-  }
   const int64_t Ti = (Ni + RT - 1) / RT, Tt = (Nt + RT - 1) / RT;
-  if ((int64_t)RT * lda * 4 >= (1L << 30) || (int64_t)RT * ldb * 4 >= (1L << 30) || Ni >= (1L << 30) || Nt >= (1L << 30) ||
-      Ti * Tt >= (1L << 31)) {
-    clipa_set_error("retrieval_ranks_multi: Ni, Nt or leading dimension too large");
-    return CLIPA_ERR_ARG;
-  }
-  const void* ptrs[8] = {A, B, txt2img, i2t_gt, i2t_eq, t2i_gt, t2i_eq, workspace};
-  for (int i = 0; i < 8; ++i)
-    if (!ptrs[i] || ((uintptr_t)ptrs[i] & 15)) { clipa_set_error("retrieval_ranks_multi: pointer argument %d is null or not 16-byte aligned", i); return CLIPA_ERR_ARG; }
-  if (((uintptr_t)scale & 3)) { clipa_set_error("retrieval_ranks_multi: scale is not 4-byte aligned"); return CLIPA_ERR_ARG; }
+  if (int rc = rank_check_args("retrieval_ranks_multi", E, lda, ldb, Ni >= (1L << 30) || Nt >= (1L << 30) || Ti * Tt >= (1L << 31),
+                               "Ni, Nt", {A, B, txt2img, i2t_gt, i2t_eq, t2i_gt, t2i_eq, workspace}, scale)) return rc;
   if (workspace_bytes < clipa_retrieval_ranks_multi_workspace(Ni, Nt)) { clipa_set_error("retrieval_ranks_multi: workspace too small"); return CLIPA_ERR_ARG; }
   int dev = 0;
   if (int rc = current_device(&dev)) return rc;
-  if (int rc = ensure_rkm_attrs(dev)) return rc;
+  if (int rc = g_rkm_lds.ensure(dev, {(const void*)retrieval_multi_kernel<true>, (const void*)retrieval_multi_kernel<false>}, 2 * R_STAGE, "retrieval_multi")) return rc;
   MultiArgs a = {};
   a.A = (const char*)A; a.B = (const char*)B; a.c = txt2img; a.Ni = (int)Ni; a.Nt = (int)Nt; a.E = (int)E;
   a.lda = lda; a.ldb = ldb; a.scale = scale;

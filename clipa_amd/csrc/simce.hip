@@ -8,8 +8,9 @@
 // three passes over them are replaced by 2 x 4 MB of partials; the bf16 gradient matrix is still materialised.)
 //
 // Tile / ring / fragments: the 256x256x64, 8-wave, v_mfma_f32_32x32x16_bf16 structure of gemm_nt2<f32> with one
-// output tile per workgroup (the loss is 0.07 % of the step's FLOPs: no persistence, no tile remap).
-#include "gemm_common.h"
+// output tile per workgroup (the loss is 0.07 % of the step's FLOPs: no persistence, no tile remap); the main loop is
+// sim_tile.h's, shared with simce_distill.hip.
+#include "sim_tile.h"
 
 namespace clipa_gemm {
 namespace {
@@ -40,63 +41,9 @@ __global__ __launch_bounds__(NTHREADS) void simce_kernel(CEArgs p) {
   const int tm = blockIdx.x / tilesN, tn = blockIdx.x - tm * tilesN;
   const int m0 = tm * BM, n0 = tn * BN;
   const int rowsA = min(BM, p.R - m0), rowsB = min(BN, p.N - n0);
-  const __amdgpu_buffer_rsrc_t rsA = make_rsrc(p.A + (size_t)m0 * p.lda * 2, (unsigned)(rowsA * p.lda * 2));
-  const __amdgpu_buffer_rsrc_t rsB = make_rsrc(p.B + (size_t)n0 * p.ldb * 2, (unsigned)(rowsB * p.ldb * 2));
 
-  unsigned voffA[4], voffB[4];
-  int kel[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int row = (j * 8 + wave) * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-    voffA[j] = (unsigned)(row * p.lda * 2 + chunk * 16);
-    voffB[j] = (unsigned)(row * p.ldb * 2 + chunk * 16);
-    kel[j] = chunk * 8;
-  }
   f32x16 acc[2][4];
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ni][mi][r] = 0.f;
-  auto stage = [&](int buf, int k0) {
-    char* sA = smem + buf * STAGE_BYTES;
-    char* sB = sA + IMG_BYTES;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int pc = j * 8 + wave;
-      const unsigned oob = (k0 + kel[j] >= p.K) ? 0x80000000u : 0u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, LDS_PTR(sA + pc * 1024), 16, voffA[j] | oob, k0 * 2, 0, 0);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, LDS_PTR(sB + pc * 1024), 16, voffB[j] | oob, k0 * 2, 0, 0);
-    }
-  };
-  const int sw = (l31 >> 1) & 7;
-  const int rowoffA = (wm * 128 + l31) * 128;
-  const int rowoffB = (wn * 64 + l31) * 128;
-  const int nkt = (p.K + BK - 1) / BK;
-  stage(0, 0);
-  for (int kt = 0; kt < nkt; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (kt + 1 < nkt) stage((kt + 1) & 1, (kt + 1) * BK);
-    const char* sA = smem + (kt & 1) * STAGE_BYTES;
-    const char* sB = sA + IMG_BYTES;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int coff = ((2 * ks + hi) ^ sw) << 4;
-      bf16x8 fa[4], fb[2];
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) fa[mi] = *(const bf16x8*)(sA + rowoffA + mi * 4096 + coff);
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) fb[ni] = *(const bf16x8*)(sB + rowoffB + ni * 4096 + coff);
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-          acc[ni][mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[ni], fa[mi], acc[ni][mi], 0, 0, 0);
-    }
-  }
+  sim_tile<4>(smem, p.A + (size_t)m0 * p.lda * 2, p.B + (size_t)n0 * p.ldb * 2, p.lda, p.ldb, p.K, rowsA, rowsB, acc);
   __syncthreads();                                   // the ring is dead: its first bytes become the cross-wave scratch
   float* red = (float*)smem;                         // [4 wn][256 rows][2]
 
@@ -175,6 +122,11 @@ __global__ __launch_bounds__(NTHREADS) void simce_kernel(CEArgs p) {
   }
 }
 
+// Instantiated explicitly: hipcc's host pass leaves the second implicit instantiation of a kernel undefined (the library
+// then fails to load) when the kernel's body calls a device function template that holds a lambda, as sim_tile does.
+template __global__ void simce_kernel<false>(CEArgs);
+template __global__ void simce_kernel<true>(CEArgs);
+
 // fwd: merge the per-tile (max, sum) partials -> lse, loss row.   bwd: sum the per-tile partials of d loss / d s.
 template <bool BWD>
 __global__ void simce_merge_kernel(const float* __restrict__ part, int tilesN, long R, const float* __restrict__ lab,
@@ -196,18 +148,18 @@ __global__ void simce_merge_kernel(const float* __restrict__ part, int tilesN, l
   }
 }
 
-std::once_flag g_ce_once[MAX_DEVICES];
-int g_ce_rc[MAX_DEVICES];
+LdsOptIn g_ce_lds;
 int ensure_ce_attrs(int dev) {
-  std::call_once(g_ce_once[dev], [dev]() {
-    g_ce_rc[dev] = 0;
-    const void* ks[2] = {(const void*)simce_kernel<false>, (const void*)simce_kernel<true>};
-    for (int i = 0; i < 2; ++i) {
-      const hipError_t e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES);
-      if (e != hipSuccess) { clipa_set_error("hipFuncSetAttribute(simce): %s", hipGetErrorString(e)); g_ce_rc[dev] = CLIPA_ERR_LAUNCH; }
-    }
-  });
-  return g_ce_rc[dev];
+  return g_ce_lds.ensure(dev, {(const void*)simce_kernel<false>, (const void*)simce_kernel<true>}, 2 * STAGE_BYTES, "simce");
+}
+
+// the fields the forward and the backward share; part = the workspace
+CEArgs make_args(const void* rows, const void* cols, int64_t R, int64_t N, int64_t E, int64_t lda, int64_t ldb,
+                 const float* scale, int64_t label0, void* workspace) {
+  CEArgs a = {};
+  a.A = (const char*)rows; a.B = (const char*)cols; a.R = (int)R; a.N = (int)N; a.K = (int)E; a.lda = lda; a.ldb = ldb;
+  a.scale = scale; a.label0 = label0; a.part = (float*)workspace;
+  return a;
 }
 
 int ce_check(int64_t R, int64_t N, int64_t E, int64_t lda, int64_t ldb, int64_t label0) {
@@ -237,9 +189,8 @@ extern "C" int clipa_simce_fwd(const void* rows, const void* cols, int64_t R, in
   if (int rc = current_device(&dev)) return rc;
   if (int rc = ensure_ce_attrs(dev)) return rc;
   const int64_t tilesN = (N + BN - 1) / BN, tilesM = (R + BM - 1) / BM;
-  CEArgs a = {};
-  a.A = (const char*)rows; a.B = (const char*)cols; a.R = (int)R; a.N = (int)N; a.K = (int)E; a.lda = lda; a.ldb = ldb;
-  a.scale = scale; a.label0 = label0; a.part = (float*)workspace; a.lab = (float*)workspace + tilesN * R * 2;
+  CEArgs a = make_args(rows, cols, R, N, E, lda, ldb, scale, label0, workspace);
+  a.lab = (float*)workspace + tilesN * R * 2;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(simce_kernel<false>, dim3((unsigned)(tilesM * tilesN)), dim3(NTHREADS), 2 * STAGE_BYTES, st, a);
   if (int rc = clipa_check_launch("simce_fwd")) return rc;
@@ -261,9 +212,8 @@ extern "C" int clipa_simce_bwd(const void* rows, const void* cols, int64_t R, in
   if (int rc = current_device(&dev)) return rc;
   if (int rc = ensure_ce_attrs(dev)) return rc;
   const int64_t tilesN = (N + BN - 1) / BN, tilesM = (R + BM - 1) / BM;
-  CEArgs a = {};
-  a.A = (const char*)rows; a.B = (const char*)cols; a.R = (int)R; a.N = (int)N; a.K = (int)E; a.lda = lda; a.ldb = ldb;
-  a.scale = scale; a.label0 = label0; a.gscale = gscale; a.part = (float*)workspace; a.lse = lse;
+  CEArgs a = make_args(rows, cols, R, N, E, lda, ldb, scale, label0, workspace);
+  a.gscale = gscale; a.lse = lse;
   a.dl = (unsigned short*)dlogits_bf16; a.ldd = ldd;    // columns [N, ldd) inside the last tile are written as zeros
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(simce_kernel<true>, dim3((unsigned)(tilesM * tilesN)), dim3(NTHREADS), 2 * STAGE_BYTES, st, a);

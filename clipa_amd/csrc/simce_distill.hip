@@ -13,17 +13,16 @@
 // Tile choice: 128 rows x 256 columns per workgroup (not simce's 256 x 256).  Both fp32 accumulator tiles are live in the
 // epilogue; at 256 x 256 that is 2 x 128 accumulator registers per lane, and with 8 waves (2 per SIMD) a wave may hold at
 // most 256 VGPR + AGPR, so the ring addresses and fragments would spill.  At 128 x 256 each wave owns 64 x 64 of both
-// tiles (2 x 64 registers).  The two GEMMs run one after the other through the same two-stage LDS ring (BK = 64,
-// v_mfma_f32_32x32x16_bf16, simce's swizzle and fragment layout), teacher first.  The loss is a small share of a step:
-// one tile per workgroup, no persistence.
-#include "gemm_common.h"
+// tiles (2 x 64 registers).  The two GEMMs run one after the other through the same two-stage LDS ring (sim_tile.h:
+// simce's main loop with an A image of 128 rows), teacher first.  The loss is a small share of a step: one tile per
+// workgroup, no persistence.
+#include "sim_tile.h"
 
 namespace clipa_gemm {
 namespace {
 
 constexpr int DBM = 128;                                  // rows per tile (BN = 256 columns)
-constexpr int D_IMG_A = DBM * BK * 2;                     // 16 KiB
-constexpr int D_STAGE = D_IMG_A + BN * BK * 2;            // + 32 KiB
+constexpr int D_STAGE = sim_stage_bytes<DBM / 64>();      // A image 16 KiB + B image 32 KiB
 constexpr int D_NPART = 5;                                // forward partials per row and tile
 
 struct DArgs {
@@ -41,76 +40,6 @@ struct DArgs {
   long ldd;
 };
 
-// acc[ni][mi] += tile of A[m0 : m0 + 128] . B[n0 : n0 + 256]^T over K; D[n][m] layout as simce.  Starts with a barrier:
-// the previous GEMM's waves may still read the ring slot this one stages first.
-__device__ __forceinline__ void dgemm_tile(char* smem, const char* A, const char* B, long lda, long ldb, int K, int rowsA,
-                                           int rowsB, f32x16 (&acc)[2][2]) {
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, hi = lane >> 5;
-  const int wm = wave >> 2, wn = wave & 3;   // wave tile: 64 (m) x 64 (n)
-  const __amdgpu_buffer_rsrc_t rsA = make_rsrc(A, (unsigned)(rowsA * lda * 2));
-  const __amdgpu_buffer_rsrc_t rsB = make_rsrc(B, (unsigned)(rowsB * ldb * 2));
-  unsigned voffA[2], voffB[4];
-  int kelA[2], kelB[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int row = (j * 8 + wave) * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((row >> 1) & 7);
-    voffB[j] = (unsigned)(row * ldb * 2 + chunk * 16);
-    kelB[j] = chunk * 8;
-    if (j < 2) { voffA[j] = (unsigned)(row * lda * 2 + chunk * 16); kelA[j] = chunk * 8; }
-  }
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ni][mi][r] = 0.f;
-  auto stage = [&](int buf, int k0) {
-    char* sA = smem + buf * D_STAGE;
-    char* sB = sA + D_IMG_A;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int pc = j * 8 + wave;
-      if (j < 2) {
-        const unsigned oob = (k0 + kelA[j] >= K) ? 0x80000000u : 0u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, LDS_PTR(sA + pc * 1024), 16, voffA[j] | oob, k0 * 2, 0, 0);
-      }
-      const unsigned oob = (k0 + kelB[j] >= K) ? 0x80000000u : 0u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, LDS_PTR(sB + pc * 1024), 16, voffB[j] | oob, k0 * 2, 0, 0);
-    }
-  };
-  const int sw = (l31 >> 1) & 7;
-  const int rowoffA = (wm * 64 + l31) * 128;
-  const int rowoffB = (wn * 64 + l31) * 128;
-  const int nkt = (K + BK - 1) / BK;
-  __syncthreads();
-  stage(0, 0);
-  for (int kt = 0; kt < nkt; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (kt + 1 < nkt) stage((kt + 1) & 1, (kt + 1) * BK);
-    const char* sA = smem + (kt & 1) * D_STAGE;
-    const char* sB = sA + D_IMG_A;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int coff = ((2 * ks + hi) ^ sw) << 4;
-      bf16x8 fa[2], fb[2];
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) fa[mi] = *(const bf16x8*)(sA + rowoffA + mi * 4096 + coff);
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) fb[ni] = *(const bf16x8*)(sB + rowoffB + ni * 4096 + coff);
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-          acc[ni][mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[ni], fa[mi], acc[ni][mi], 0, 0, 0);
-    }
-  }
-}
-
 template <bool BWD>
 __global__ __launch_bounds__(NTHREADS) void simce_distill_kernel(DArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -125,8 +54,9 @@ __global__ __launch_bounds__(NTHREADS) void simce_distill_kernel(DArgs p) {
   const int rowsA = min(DBM, p.R - m0), rowsB = min(BN, p.N - n0);
 
   f32x16 acc_t[2][2], acc_s[2][2];
-  dgemm_tile(smem, p.At + (size_t)m0 * p.ldat * 2, p.Bt + (size_t)n0 * p.ldbt * 2, p.ldat, p.ldbt, p.Kt, rowsA, rowsB, acc_t);
-  dgemm_tile(smem, p.As + (size_t)m0 * p.ldas * 2, p.Bs + (size_t)n0 * p.ldbs * 2, p.ldas, p.ldbs, p.Ks, rowsA, rowsB, acc_s);
+  sim_tile<2>(smem, p.At + (size_t)m0 * p.ldat * 2, p.Bt + (size_t)n0 * p.ldbt * 2, p.ldat, p.ldbt, p.Kt, rowsA, rowsB, acc_t);
+  __syncthreads();                                   // the teacher's last step may still read the ring slot staged next
+  sim_tile<2>(smem, p.As + (size_t)m0 * p.ldas * 2, p.Bs + (size_t)n0 * p.ldbs * 2, p.ldas, p.ldbs, p.Ks, rowsA, rowsB, acc_s);
   __syncthreads();                                   // the ring is dead: its first bytes become the cross-wave scratch
   float* red = (float*)smem;                         // fwd [4 wn][128 rows][5], bwd [4 wn][128 rows]
 
@@ -231,6 +161,11 @@ __global__ __launch_bounds__(NTHREADS) void simce_distill_kernel(DArgs p) {
   }
 }
 
+// Instantiated explicitly: hipcc's host pass leaves the second implicit instantiation of a kernel undefined (the library
+// then fails to load) when the kernel's body calls a device function template that holds a lambda, as sim_tile does.
+template __global__ void simce_distill_kernel<false>(DArgs);
+template __global__ void simce_distill_kernel<true>(DArgs);
+
 // fwd: merge the per-tile partials -> lse_s, lse_t, ce_rows, dist_rows.   bwd: sum the per-tile partials of d loss / d s
 // into ce_rows (the caller's dscale_rows).
 template <bool BWD>
@@ -266,18 +201,9 @@ __global__ void simce_distill_merge_kernel(const float* __restrict__ part, int t
   }
 }
 
-std::once_flag g_dce_once[MAX_DEVICES];
-int g_dce_rc[MAX_DEVICES];
+LdsOptIn g_dce_lds;
 int ensure_dce_attrs(int dev) {
-  std::call_once(g_dce_once[dev], [dev]() {
-    g_dce_rc[dev] = 0;
-    const void* ks[2] = {(const void*)simce_distill_kernel<false>, (const void*)simce_distill_kernel<true>};
-    for (int i = 0; i < 2; ++i) {
-      const hipError_t e = hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize, 2 * D_STAGE);
-      if (e != hipSuccess) { clipa_set_error("hipFuncSetAttribute(simce_distill): %s", hipGetErrorString(e)); g_dce_rc[dev] = CLIPA_ERR_LAUNCH; }
-    }
-  });
-  return g_dce_rc[dev];
+  return g_dce_lds.ensure(dev, {(const void*)simce_distill_kernel<false>, (const void*)simce_distill_kernel<true>}, 2 * D_STAGE, "simce_distill");
 }
 
 int dce_check(int64_t R, int64_t N, int64_t Es, int64_t Et, int64_t ldas, int64_t ldbs, int64_t ldat, int64_t ldbt,
@@ -292,6 +218,17 @@ int dce_check(int64_t R, int64_t N, int64_t Es, int64_t Et, int64_t ldas, int64_
   if (256 * ldmax * 2 >= (1L << 30)) { clipa_set_error("simce_distill: leading dimension too large"); return CLIPA_ERR_ARG; }
   if (R >= (1L << 30) || N >= (1L << 30)) { clipa_set_error("simce_distill: R or N too large"); return CLIPA_ERR_ARG; }
   return 0;
+}
+
+// the fields the forward and the backward share; part = the workspace
+DArgs make_args(const void* rows_s, const void* cols_s, const void* rows_t, const void* cols_t, int64_t R, int64_t N,
+                int64_t Es, int64_t Et, int64_t ldas, int64_t ldbs, int64_t ldat, int64_t ldbt, const float* scale_s,
+                const float* scale_t, int64_t label0, void* workspace) {
+  DArgs a = {};
+  a.As = (const char*)rows_s; a.Bs = (const char*)cols_s; a.At = (const char*)rows_t; a.Bt = (const char*)cols_t;
+  a.R = (int)R; a.N = (int)N; a.Ks = (int)Es; a.Kt = (int)Et; a.ldas = ldas; a.ldbs = ldbs; a.ldat = ldat; a.ldbt = ldbt;
+  a.scale_s = scale_s; a.scale_t = scale_t; a.label0 = label0; a.part = (float*)workspace;
+  return a;
 }
 
 }  // namespace
@@ -317,11 +254,8 @@ extern "C" int clipa_simce_distill_fwd(const void* rows_s, const void* cols_s, c
   if (int rc = current_device(&dev)) return rc;
   if (int rc = ensure_dce_attrs(dev)) return rc;
   const int64_t tilesN = (N + BN - 1) / BN, tilesM = (R + DBM - 1) / DBM;
-  DArgs a = {};
-  a.As = (const char*)rows_s; a.Bs = (const char*)cols_s; a.At = (const char*)rows_t; a.Bt = (const char*)cols_t;
-  a.R = (int)R; a.N = (int)N; a.Ks = (int)Es; a.Kt = (int)Et; a.ldas = ldas; a.ldbs = ldbs; a.ldat = ldat; a.ldbt = ldbt;
-  a.scale_s = scale_s; a.scale_t = scale_t; a.label0 = label0;
-  a.part = (float*)workspace; a.lab = (float*)workspace + tilesN * R * D_NPART;
+  DArgs a = make_args(rows_s, cols_s, rows_t, cols_t, R, N, Es, Et, ldas, ldbs, ldat, ldbt, scale_s, scale_t, label0, workspace);
+  a.lab = (float*)workspace + tilesN * R * D_NPART;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(simce_distill_kernel<false>, dim3((unsigned)(tilesM * tilesN)), dim3(NTHREADS), 2 * D_STAGE, st, a);
   if (int rc = clipa_check_launch("simce_distill_fwd")) return rc;
@@ -346,11 +280,8 @@ extern "C" int clipa_simce_distill_bwd(const void* rows_s, const void* cols_s, c
   if (int rc = current_device(&dev)) return rc;
   if (int rc = ensure_dce_attrs(dev)) return rc;
   const int64_t tilesN = (N + BN - 1) / BN, tilesM = (R + DBM - 1) / DBM;
-  DArgs a = {};
-  a.As = (const char*)rows_s; a.Bs = (const char*)cols_s; a.At = (const char*)rows_t; a.Bt = (const char*)cols_t;
-  a.R = (int)R; a.N = (int)N; a.Ks = (int)Es; a.Kt = (int)Et; a.ldas = ldas; a.ldbs = ldbs; a.ldat = ldat; a.ldbt = ldbt;
-  a.scale_s = scale_s; a.scale_t = scale_t; a.label0 = label0; a.gscale = gscale; a.gc = g_c; a.gd = g_d;
-  a.part = (float*)workspace; a.lse_s = lse_s; a.lse_t = lse_t;
+  DArgs a = make_args(rows_s, cols_s, rows_t, cols_t, R, N, Es, Et, ldas, ldbs, ldat, ldbt, scale_s, scale_t, label0, workspace);
+  a.gscale = gscale; a.gc = g_c; a.gd = g_d; a.lse_s = lse_s; a.lse_t = lse_t;
   a.dl = (unsigned short*)dlogits_bf16; a.ldd = ldd;    // columns [N, ldd) inside the last tile are written as zeros
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(simce_distill_kernel<true>, dim3((unsigned)(tilesM * tilesN)), dim3(NTHREADS), 2 * D_STAGE, st, a);
