@@ -301,10 +301,25 @@ __global__ void l2norm_fwd_kernel(const float* __restrict__ x, float* __restrict
   const int lane = threadIdx.x & 63;
   const long r = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (r >= rows) return;
-  float ss = 0.f;
-  for (int i = lane; i < E; i += 64) { const float v = x[(size_t)r * E + i]; ss += v * v; }
+  float ss = 0.f, amax = 0.f;
+  for (int i = lane; i < E; i += 64) { const float v = x[(size_t)r * E + i]; ss += v * v; amax = fmaxf(amax, fabsf(v)); }
   ss = wave_sum(ss);
-  const float inv = 1.0f / fmaxf(sqrtf(ss), eps);
+  float nrm = sqrtf(ss);
+  // fp32 squares overflow for ||x|| above ~1e19 and fall into the denormals below ~1e-19: such rows (only - every other row keeps
+  // the plain sum) are summed again on values scaled by a power of two, which is exact.  The branch is uniform over the wave.
+  if (!(ss <= 1e30f) || ss < 1e-30f) {
+    amax = wave_max(amax);
+    if (amax > 0.f && amax <= 3.4e38f) {
+      int e;
+      (void)frexpf(amax, &e);
+      e = e < -126 ? -126 : (e > 127 ? 127 : e);       // 2^-e stays a normal number: no reliance on fp32 denormals
+      const float s = ldexpf(1.0f, -e);
+      float s2 = 0.f;
+      for (int i = lane; i < E; i += 64) { const float v = x[(size_t)r * E + i] * s; s2 += v * v; }
+      nrm = ldexpf(sqrtf(wave_sum(s2)), e);
+    }
+  }
+  const float inv = 1.0f / fmaxf(nrm, eps);
   for (int i = lane; i < E; i += 64) {
     const float v = x[(size_t)r * E + i] * inv;
     y[(size_t)r * E + i] = v;
@@ -375,11 +390,14 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float* __restri
 template <bool IN_F32>
 __global__ void cast_to_bf16_kernel(const void* __restrict__ in, unsigned short* __restrict__ out, long n) {
   for (long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 8; i < n; i += (long)gridDim.x * blockDim.x * 8) {
-    float v[8];
     if (i + 8 <= n) {
-      if (IN_F32) { *(float4*)v = *(const float4*)((const float*)in + i); *(float4*)(v + 4) = *(const float4*)((const float*)in + i + 4); }
-      else unpack8(*(const u32x4*)((const unsigned short*)in + i), v);
-      *(u32x4*)(out + i) = pack8(v);
+      if (IN_F32) {
+        float v[8];
+        *(float4*)v = *(const float4*)((const float*)in + i); *(float4*)(v + 4) = *(const float4*)((const float*)in + i + 4);
+        *(u32x4*)(out + i) = pack8(v);
+      } else {
+        *(u32x4*)(out + i) = *(const u32x4*)((const unsigned short*)in + i);     // a copy, bit for bit like the tail (a round trip through f32 would quiet a signalling NaN)
+      }
     } else {
       for (long j = i; j < n; ++j) out[j] = IN_F32 ? f2bf(((const float*)in)[j]) : ((const unsigned short*)in)[j];
     }
@@ -594,15 +612,16 @@ __global__ void scatter_rows_kernel(const unsigned short* __restrict__ dy, const
 
 extern "C" int clipa_gather_rows(const void* x, const int64_t* rows, void* out, int64_t n_out, int64_t n_src, int64_t D,
                                  void* stream) {
-  if (D % 8 != 0 || !rows) { clipa_set_error("gather_rows: D%%8 != 0 or no row list"); return CLIPA_ERR_ARG; }
-  if (n_out <= 0) return CLIPA_OK;
+  if (D % 8 != 0) { clipa_set_error("gather_rows: D%%8 != 0"); return CLIPA_ERR_ARG; }
+  if (n_out <= 0) return CLIPA_OK;               // an empty row list has no storage to point at
+  if (!rows) { clipa_set_error("gather_rows: no row list"); return CLIPA_ERR_ARG; }
   hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(n_out * (D / 8))), dim3(256), 0, (hipStream_t)stream,
                      (const unsigned short*)x, rows, (unsigned short*)out, (long)n_out, (long)n_src, (int)D);
   return clipa_check_launch("gather_rows");
 }
 extern "C" int clipa_scatter_rows(const void* dy, const int64_t* rows, void* dx, int64_t n_src, int64_t n_dst, int64_t D,
                                   void* stream) {
-  if (D % 8 != 0 || !rows) { clipa_set_error("scatter_rows: D%%8 != 0 or no row list"); return CLIPA_ERR_ARG; }
+  if (D % 8 != 0 || (!rows && n_src > 0)) { clipa_set_error("scatter_rows: D%%8 != 0 or no row list"); return CLIPA_ERR_ARG; }
   if (n_dst <= 0) return CLIPA_OK;
   const hipError_t e = hipMemsetAsync(dx, 0, (size_t)n_dst * D * 2, (hipStream_t)stream);
   if (e != hipSuccess) { clipa_set_error("scatter_rows: memset: %s", hipGetErrorString(e)); return CLIPA_ERR_LAUNCH; }

@@ -127,8 +127,8 @@ __global__ void sqnorm_reduce_kernel(const float* __restrict__ partials, long n,
 __global__ void clip_coef_kernel(const float* __restrict__ acc, float max_norm, float* __restrict__ norm_out, float* __restrict__ coef_out) {
   const float n = sqrtf(acc[0]);
   if (norm_out) norm_out[0] = n;
-  const float c = max_norm / (n + 1e-6f);      // torch.nn.utils.clip_grad_norm_: clip_coef clamped to <= 1
-  coef_out[0] = c < 1.0f ? c : 1.0f;
+  const float c = max_norm / (n + 1e-6f);      // torch.nn.utils.clip_grad_norm_: torch.clamp(clip_coef, max=1.0)
+  coef_out[0] = c > 1.0f ? 1.0f : c;           // a NaN norm gives a NaN coefficient (as clamp does): every update is poisoned
 }
 }  // namespace
 

@@ -1203,14 +1203,16 @@ def grad_sqnorm(grads, buf=None):
 
 
 def clip_coef(buf, max_norm):
-    """buf[0] = sum of squares -> (total_norm, coef) device scalars (views of buf), coef = min(1, max_norm / (norm + 1e-6))."""
+    """buf[0] = sum of squares -> (total_norm, coef) device scalars (views of buf), coef = clamp(max_norm / (norm + 1e-6), max=1):
+    1 below the threshold, 0 for an infinite norm, NaN for a NaN norm (torch.nn.utils.clip_grad_norm_)."""
     lib.call("clipa_clip_coef", _p(buf), float(max_norm), ctypes.c_void_p(buf.data_ptr() + 4), ctypes.c_void_p(buf.data_ptr() + 8),
              _stream())
     return buf[1], buf[2]
 
 
 def grad_clip_coef(grads, max_norm):
-    """clip_grad_norm_ on the device: -> (total_norm, coef) f32 device scalars, coef = min(1, max_norm / (norm + 1e-6))."""
+    """clip_grad_norm_ on the device: -> (total_norm, coef) f32 device scalars, coef = clamp(max_norm / (norm + 1e-6), max=1)
+    (NaN when any gradient element is NaN)."""
     return clip_coef(grad_sqnorm(grads), max_norm)
 
 

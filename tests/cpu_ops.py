@@ -237,7 +237,13 @@ def embed_tokens(ids, table, pos):
 def embed_tokens_bwd(ids, dx, vocab, need_table=True, need_pos=True):
     B, T = ids.shape
     D = dx.shape[1]
-    dt = torch.zeros(vocab, D).index_add_(0, ids.reshape(-1), dx.float()) if need_table else None
+    dt = None
+    if need_table:      # the kernel's contract, bit for bit: an exact sum rounded once to f32, finite elements saturate at
+        d = dx.double()     # +-2^17, a table row that receives a non-finite element is NaN
+        ok = d.isfinite()
+        d = torch.where(ok, d.clamp(-131072.0, 131072.0), torch.zeros_like(d))
+        dt = torch.zeros(vocab, D, dtype=torch.float64).index_add_(0, ids.reshape(-1), d).float()
+        dt[ids.reshape(-1)[~ok.all(1)]] = float("nan")
     dp = dx.float().reshape(B, T, D).sum(0) if need_pos else None
     return dt, dp
 
@@ -246,34 +252,34 @@ def argmax_tokens(ids):
     return ids.argmax(-1).to(torch.int32)
 
 
-def _pool(x3, mode, idx):
-    B = x3.shape[0]
-    if mode == POOL_FIRST:
-        return x3[:, 0]
-    if mode == POOL_LAST:
-        return x3[:, -1]
-    if mode == POOL_INDEX:
-        return x3[torch.arange(B), idx.long()]
-    if mode == POOL_MEAN_ALL:
-        return x3.mean(1)
-    return x3[:, 1:].mean(1)
+def _pool_span(mode, L):
+    return {POOL_FIRST: (0, 1), POOL_LAST: (L - 1, L), POOL_MEAN_ALL: (0, L), POOL_MEAN_PATCH: (1, L)}[mode]
 
 
 def pool_fwd(x, B, L, mode, idx=None):
-    return _pool(x.float().reshape(B, L, -1), mode, idx)
+    """The kernel's arithmetic: f32 sum over the tokens times f32(1 / n)."""
+    x3 = x.float().reshape(B, L, -1)
+    if mode == POOL_INDEX:
+        return x3[torch.arange(B), idx.long()]
+    l0, l1 = _pool_span(mode, L)
+    return x3[:, l0:l1].sum(1) * (torch.ones(()) / float(l1 - l0))
 
 
 def pool_bwd(dout, B, L, mode, idx=None):
-    x = torch.zeros(B, L, dout.shape[-1], requires_grad=True)
-    with torch.enable_grad():
-        _pool(x, mode, idx).backward(dout.float())
-    return x.grad.reshape(B * L, -1).to(bf16)
+    """dx = dout * f32(1 / n) on the pooled tokens (one rounding to bf16), zero elsewhere."""
+    dx = torch.zeros(B, L, dout.shape[-1], dtype=bf16)
+    if mode == POOL_INDEX:
+        dx[torch.arange(B), idx.long()] = dout.float().to(bf16)
+    else:
+        l0, l1 = _pool_span(mode, L)
+        dx[:, l0:l1] = (dout.float() * (torch.ones(()) / float(l1 - l0))).to(bf16)[:, None]
+    return dx.reshape(B * L, -1)
 
 
 def l2norm_fwd(x, eps=1e-12, want_bf16=False):
-    n = x.norm(dim=-1).clamp_min(eps)
-    y = x / n[:, None]
-    return y, (y.to(bf16) if want_bf16 else None), 1.0 / n
+    n = x.double().norm(dim=-1).clamp_min(eps)      # in fp64: the kernel takes rows whose f32 squares overflow / underflow
+    y = (x.double() / n[:, None]).float()
+    return y, (y.to(bf16) if want_bf16 else None), (1.0 / n).float()
 
 
 def l2norm_bwd(y, inv, dy):
@@ -364,8 +370,16 @@ def grad_clip_coef(grads, max_norm):
 
 
 def reduce_shards(pieces, world, out=None, scale=None, out_dtype=None):
+    """The kernel's arithmetic, bit for bit: f32 additions in rank order, one multiply, one rounding."""
     n = pieces.numel() // world
-    r = pieces.float().view(world, n).sum(0) * (1.0 / world if scale is None else scale)
+    if n * world != pieces.numel():
+        raise RuntimeError("reduce_shards: numel must be a multiple of world")
+    if n % 8 != 0:
+        raise RuntimeError("reduce_shards: n must be a multiple of 8 and W > 0")
+    r = torch.zeros(n)
+    for w in range(world):
+        r = r + pieces.view(world, n)[w].float()
+    r = r * torch.tensor(1.0 / world if scale is None else scale, dtype=f32)
     if out is None:
         return r.to(out_dtype or pieces.dtype)
     out.copy_(r)
@@ -373,13 +387,14 @@ def reduce_shards(pieces, world, out=None, scale=None, out_dtype=None):
 
 
 def gather_rows(x, rows):
-    out = x[rows.clamp_min(0)].contiguous()
-    out[rows < 0] = 0                       # rows outside [0, n) read zeros, as the kernel does
+    ok = (rows >= 0) & (rows < x.shape[0])
+    out = torch.zeros((rows.numel(), x.shape[1]), dtype=x.dtype)       # rows outside [0, n) read zeros, as the kernel does
+    out[ok] = x[rows[ok]]
     return out
 
 
 def scatter_rows(dy, rows, n_dst):
     dx = torch.zeros((n_dst, dy.shape[1]), dtype=dy.dtype)
-    ok = rows >= 0
+    ok = (rows >= 0) & (rows < n_dst)                                  # ... and are skipped here
     dx[rows[ok]] = dy[ok]
     return dx
