@@ -13,15 +13,14 @@
 // saturates): dW = sum_m dY[m,:]^T X[m,:] = t * sum_m dq[m,:]^T Q8[m,:].  t stays on the device (alpha_dev).
 //
 // gemm_tn8_kernel: whole 256 x 256 tiles, split-M slices of an even number (>= 4) of 128-row K steps - the structure of
-// gemm_tna.hip (one wave per SIMD, 128 x 128 wave tile in a[0:255], the K loop ONE generated inline-asm statement,
+// gemm_tna.hip (gemm_4w.h: one wave per SIMD, 128 x 128 wave tile in a[0:255], the K loop ONE generated inline-asm statement,
 // tools/gen_gemm_tn8.py -> gemm_tn8_asm.inc) with gemm_f8a.hip's step (64 MFMAs over 128 k-values from 128 registers of
 // fragments, read-ahead following the registers as they die).  Fragments: `ds_read_b64_tr_b8` over [128 m][256 B] LDS images
 // filled by LDS-DMA with a source-side chunk swizzle.  fp32 split-M slabs + a fixed-order reduce that applies alpha.
 // gemm_tn8_generic_kernel: any shape (test-size models, ragged row counts): the same MFMA fed by byte gathers from global
 // memory; also takes the row remainder of a whole-tile product as one more slab.
-#include "gemm_common.h"
+#include "gemm_4w.h"
 #include "gemm_tn8_asm.inc"
-#include <utility>
 
 namespace clipa_gemm {
 namespace {
@@ -38,27 +37,6 @@ struct TN8Args {
 
 constexpr int TN8_THREADS = 256;
 constexpr int TN8_LDS = 2 * STAGE_BYTES;
-
-template <int IDX>
-__device__ __forceinline__ float t8acc_rd() {
-  float x;
-  asm volatile("v_accvgpr_read_b32 %0, a[%1]" : "=v"(x) : "n"(IDX));
-  return x;
-}
-// block I = 8 ri + ci of the wave's 8 x 8: lane holds O[rblock + 4 (lane >> 4) + e][cblock + (lane & 15)], e = 0..3
-template <int I>
-__device__ __forceinline__ void tn8_store_block(float* o, long ldo) {
-  constexpr int RI = I >> 3, CI = I & 7;
-  float* q = o + (size_t)(RI * 16) * ldo + CI * 16;
-  q[0] = t8acc_rd<4 * I + 0>();
-  q[ldo] = t8acc_rd<4 * I + 1>();
-  q[2 * ldo] = t8acc_rd<4 * I + 2>();
-  q[3 * ldo] = t8acc_rd<4 * I + 3>();
-}
-template <int... Is>
-__device__ __forceinline__ void tn8_store_all(float* o, long ldo, std::integer_sequence<int, Is...>) {
-  (tn8_store_block<Is>(o, ldo), ...);
-}
 
 #define TN8_OPERANDS                                                                                                        \
   : [skP] "=&s"(skP), [skQ] "=&s"(skQ), [cnt] "=&s"(cnt)                                                                    \
@@ -139,7 +117,7 @@ __global__ __launch_bounds__(TN8_THREADS) void gemm_tn8_kernel(TN8Args p) {
   asm volatile("" : "+v"(tid_e));
   const int g4e = (tid_e & 63) >> 4, i16e = tid_e & 15;
   float* O = p.O + (size_t)slice * p.R * p.ldo + (size_t)(r0 + wr * 128 + 4 * g4e) * p.ldo + (c0 + wc * 128 + i16e);
-  tn8_store_all(O, p.ldo, std::make_integer_sequence<int, 64>{});
+  acc_store_tile(O, p.ldo);
 }
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));

@@ -5,44 +5,21 @@
 // Same reference call sites as gemm_tn.hip (the autograd transposes of nn.Linear / in-proj / out-proj,
 // clipa_torch/open_clip/transformer.py:209,217-219,234), same split-M fp32 slabs + reduce_slabs_kernel, same LDS image
 // ([64 m][256] bf16, tn_swz16) and `ds_read_b64_tr_b16` fragments as gemm_tn3_kernel.  What differs is the execution structure
-// (the one gemm_nta.hip introduced for the NT product): one wave per SIMD with a 128 x 128 wave tile (64 accumulator blocks in
+// (gemm_4w.h: the one gemm_nta.hip introduced for the NT product): one wave per SIMD with a 128 x 128 wave tile (64 accumulator blocks in
 // a[0:255]), all 32 fragments of a K step in registers so that the LDS slot is re-filled two steps ahead, and the whole K loop
 // of the workgroup as ONE generated inline-asm statement (tools/gen_gemm_tna.py -> gemm_tna_asm.inc).  The weight-gradient
 // product has no epilogue to speak of (one fp32 tile per ~800 K steps), so its rate is its main loop's - which in gemm_tn2/3
 // is issue- and latency-bound (64 transposing reads per wave and step between barriers), not power-bound like gemm_nt's.
 // The bias gradient (column sums of P = dY) rides the matrix pipe: P^T . ones, 16 extra MFMAs per step in the workgroups of
 // tile column 0 only.
-#include "gemm_common.h"
+#include "gemm_4w.h"
 #include "gemm_tna_asm.inc"
-#include <utility>
 
 namespace clipa_gemm {
 namespace {
 
 constexpr int TNA_THREADS = 256;
 constexpr int TNA_LDS = 2 * STAGE_BYTES;
-
-template <int IDX>
-__device__ __forceinline__ float tacc_rd() {
-  float x;
-  asm volatile("v_accvgpr_read_b32 %0, a[%1]" : "=v"(x) : "n"(IDX));
-  return x;
-}
-
-// block I = 8 ri + ci of the wave's 8 x 8: lane holds O[rblock + 4 (lane >> 4) + e][cblock + (lane & 15)], e = 0..3
-template <int I>
-__device__ __forceinline__ void tna_store_block(float* o, long ldo) {
-  constexpr int RI = I >> 3, CI = I & 7;
-  float* q = o + (size_t)(RI * 16) * ldo + CI * 16;
-  q[0] = tacc_rd<4 * I + 0>();
-  q[ldo] = tacc_rd<4 * I + 1>();
-  q[2 * ldo] = tacc_rd<4 * I + 2>();
-  q[3 * ldo] = tacc_rd<4 * I + 3>();
-}
-template <int... Is>
-__device__ __forceinline__ void tna_store_all(float* o, long ldo, std::integer_sequence<int, Is...>) {
-  (tna_store_block<Is>(o, ldo), ...);
-}
 
 #define TNA_INPUTS                                                                                                          \
   [vP] "v"(vP), [vQ] "v"(vQ), [vPe] "v"(vPe), [vPo] "v"(vPo), [vQe] "v"(vQe), [vQo] "v"(vQo), [curP] "s"(useP),             \
@@ -127,7 +104,7 @@ __global__ __launch_bounds__(TNA_THREADS) void gemm_tna_kernel(TNArgs p) {
 
   // fp32 tile of this slice: lane holds rows rblock + 4 g4 + e, column cblock + i16
   float* O = p.O + (size_t)slice * p.R * p.ldo + (size_t)(r0 + wr * 128 + 4 * g4) * p.ldo + (c0 + wc * 128 + i16);
-  tna_store_all(O, p.ldo, std::make_integer_sequence<int, 64>{});
+  acc_store_tile(O, p.ldo);
   if (do_colsum && wc == 0 && i16 == 0) {
     // every column of P^T . ones holds the same sums: take column 0.  Block ri, element e -> P column r0 + 128 wr + 16 ri + 4 g4 + e
     float* c = p.colsum + (size_t)slice * p.R + r0 + wr * 128 + 4 * g4;
