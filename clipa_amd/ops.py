@@ -3,7 +3,6 @@ current-stream plumbing.  No arithmetic happens here - every op below is one or 
 """
 import ctypes
 import math
-
 import threading
 
 import torch
@@ -11,20 +10,25 @@ import torch
 from . import lib
 
 EPI_NONE, EPI_ACT, EPI_ADD, EPI_DACT = 0, 1, 2, 3
+EPI_ACT_PRE8, EPI_DACT8 = 4, 5      # include/clipa_hip.h: e4m3 pre-activation copy / e4m3 second operand (whole-tile shapes)
 ACT_GELU_ERF, ACT_GELU_TANH, ACT_QUICK_GELU = 0, 1, 2
 DT_U8, DT_BF16, DT_F32 = 0, 1, 2
 POOL_FIRST, POOL_LAST, POOL_INDEX, POOL_MEAN_ALL, POOL_MEAN_PATCH = 0, 1, 2, 3, 4
+FMT_E4M3, FMT_E5M2 = 0, 1
 
 bf16 = torch.bfloat16
 f32 = torch.float32
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
+u8 = torch.uint8
 
 # ---- optional per-launch timing (bench.py roofline): HIP events on the launch stream ------------
 _PROF = None
+_DETAIL = False      # profile_start(detail=True): additionally key the records by shape ("gemm_nt|M,N,K,epi")
+
+# Out-of-range token ids: nn.Embedding raises; the kernels count them into a device int32 instead of clamping silently.
+# The count is fetched without stalling the stream (pinned buffer + event) and checked at the next embedding call or by
+# `check_token_ids()`: a bad id surfaces as a RuntimeError at most one step late.
+_OOB_PENDING = []
+_OOB_LOCK = threading.Lock()      # appended to from the autograd thread (embed_tokens_bwd), drained from the main thread
 
 
 def profile_start(detail=False):
@@ -45,9 +49,6 @@ def profile_stop():
         out[name] = {"launches": len(recs), "ms": sum(r[0].elapsed_time(r[1]) for r in recs),
                      "work": float(sum(r[2] for r in recs)), "bytes": float(sum(r[3] for r in recs))}
     return out
-
-
-_DETAIL = False      # profile_start(detail=True): additionally key the records by shape ("gemm_nt|M,N,K,epi")
 
 
 class _Timed:
@@ -71,6 +72,11 @@ class _Timed:
             if _DETAIL and self.tag is not None:
                 _PROF.setdefault(f"{self.name}|{self.tag}", []).append((self.a, b, self.work, self.nbytes))
         return False
+
+
+# ---- helpers ---------------------------------------------------------------------------------------
+def _stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _p(t):
@@ -101,12 +107,214 @@ def _rowmajor(t):
     return t, t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
-EPI_ACT_PRE8, EPI_DACT8 = 4, 5      # include/clipa_hip.h: e4m3 pre-activation copy / e4m3 second operand (whole-tile shapes)
+def _workspace(name, *dims, device, dtype=f32, floor=4):
+    """The scratch buffer of a kernel, sized by the library's own query `name(*dims)`: -> (buffer, its size in bytes as the kernel
+    wants it passed).  floor: the smallest allocation in bytes (a query may answer 0; a null pointer would be an argument error)."""
+    wsb = lib.query(name, *dims)
+    return torch.empty(max(wsb, floor) // dtype.itemsize, device=device, dtype=dtype), wsb
 
 
-def _whole_tiles(M, N, K):
-    """Shapes the four-wave GEMM kernel takes (gemm_nta.hip: nta_eligible): the fused e4m3 epilogues exist only there."""
-    return M % 256 == 0 and N % 256 == 0 and K % 128 == 0 and K >= 256
+def _qkv_ptrs(t, D):
+    """The q | k | v column blocks of a bf16 [rows, 3D] matrix (or of its gradient) as three pointers."""
+    base = t.data_ptr()
+    return ctypes.c_void_p(base), ctypes.c_void_p(base + 2 * D), ctypes.c_void_p(base + 4 * D)
+
+
+def _aligned_rows(x):
+    """[N, E] f32 -> (row-major tensor, row stride) with 16-byte aligned rows, as the retrieval kernels load them: a matrix that
+    is not becomes an [N, E] view of a fresh [N, E rounded up to 4] buffer."""
+    x, ld = _rowmajor(x)
+    if ld % 4 or x.data_ptr() % 16:
+        n, e = x.shape
+        buf = torch.empty((n, (e + 3) // 4 * 4), device=x.device, dtype=x.dtype)
+        buf[:, :e] = x
+        x, ld = buf[:, :e], buf.shape[1]
+    return x, ld
+
+
+def _scalar1(scale):
+    """An optional f32 device scalar as the contiguous [1] tensor the kernels read."""
+    if scale is None:
+        return None
+    _chk(scale, f32, "scale")
+    return scale.reshape(1).contiguous()
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _numel_array(tensors):
+    return (ctypes.c_int64 * len(tensors))(*[t.numel() for t in tensors])
+
+
+# ---- NT GEMMs: one planning step, one launch path ----------------------------------------------------
+def _whole_tiles(M, N, K, f8=False):
+    """Shapes the four-wave GEMM kernels take (gemm_nta.hip: nta_eligible; f8=True: gemm_f8a.hip: f8a_eligible, whose K tile is
+    twice as deep): the fused e4m3 epilogues exist only there."""
+    kt = 256 if f8 else 128
+    return M % 256 == 0 and N % 256 == 0 and K % kt == 0 and K >= 2 * kt
+
+
+def _plan_nt(M, N, K, *, f8, epi, want_pre, aux8, want_act=False, out_f32=False, dense_out=True, fmt_b=FMT_E4M3, sa=True,
+             bias=False, out_scale=False, want_colsum=False, emit=False):
+    """How an NT GEMM request is served: -> (entry point, epilogue code, unfused steps).  Every extra of a request (an e4m3
+    pre-activation copy, an e4m3 second operand, its activation, a quantised output, the emitted weight-gradient operand) is
+    written by the GEMM's own epilogue where a kernel for it exists - whole-tile shapes, e4m3 weights - and is otherwise one
+    more launch before or after a plainer GEMM, named in `unfused`: "decode_aux" (e4m3_to_bf16 before), "cast_pre" (cast_e4m3
+    of the bf16 pre-activation), "act" (activation_fwd of the operand), "quantize" (scale_quantize_rows [+ colsum] of the bf16
+    output), "emit" (scale_quantize_rows of the operand)."""
+    whole = _whole_tiles(M, N, K, f8) and fmt_b == FMT_E4M3
+    entry, unfused = "clipa_gemm_nt_f8" if f8 else "clipa_gemm_nt", []
+    if emit:
+        if whole and sa:
+            entry = "clipa_gemm_nt_f8_emit"
+        else:
+            unfused.append("emit")
+    if out_scale:
+        if whole and ((epi == EPI_ACT and not want_colsum) or (epi == EPI_DACT and aux8 and not bias)):
+            entry = "clipa_gemm_nt_f8q"
+        else:
+            unfused.append("quantize")
+    if want_act and not (whole and dense_out):
+        unfused.append("act")
+    if want_pre == "e4m3" and not (epi == EPI_ACT and not out_f32 and whole):
+        unfused.append("cast_pre")
+    if aux8 and not whole:
+        unfused.append("decode_aux")
+    code = EPI_DACT8 if aux8 and whole else EPI_ACT_PRE8 if want_pre == "e4m3" and "cast_pre" not in unfused else epi
+    return entry, code, unfused
+
+
+def _gemm_nt(who, a, b, bias=None, *, sa=None, sb=None, epi=EPI_NONE, act=ACT_GELU_ERF, aux=None, alpha=1.0, out_f32=False,
+             want_pre=False, out=None, want_act=False, fmt_a=FMT_E4M3, fmt_b=FMT_E4M3, out_scale=None, want_colsum=False, emit=None):
+    """The launch path of gemm_nt (who = "gemm_nt": bf16 operands) and of gemm_nt_f8 / gemm_nt_f8_emit ("gemm_nt_f8": fp8 bytes
+    with row scales sa, sb; emit = the tensor scale t).  -> (C, pre-activation or activation | None, column sums | None, emitted
+    operand | None), fused or not as _plan_nt says."""
+    f8 = who == "gemm_nt_f8"
+    aux8 = aux is not None and aux.dtype == u8
+    if aux8 and epi != EPI_DACT:
+        raise RuntimeError(f"{who}: an e4m3 (uint8) second operand goes with EPI_DACT only")
+    _chk(a, u8 if f8 else bf16, "a8" if f8 else "a", 2)
+    _chk(b, u8 if f8 else bf16, "b8" if f8 else "b", 2)
+    a, lda = _rowmajor(a)
+    b, ldb = _rowmajor(b)
+    M, K = a.shape
+    N, Kb = b.shape
+    entry, code, unfused = _plan_nt(M, N, K, f8=f8, epi=epi, want_pre=want_pre, aux8=aux8, want_act=want_act, out_f32=out_f32,
+                                    dense_out=out is None or out.stride(0) == N, fmt_b=fmt_b, sa=sa is not None,
+                                    bias=bias is not None, out_scale=out_scale is not None, want_colsum=want_colsum,
+                                    emit=emit is not None)
+    fused_emit, fused_q = entry == "clipa_gemm_nt_f8_emit", entry == "clipa_gemm_nt_f8q"
+    if "cast_pre" in unfused:
+        out_f32 = False      # GEMM + cast has always answered in bf16, whatever out_f32 asked for
+    if fused_emit:
+        _chk(emit, f32, "t")
+        if Kb != K or tuple(aux.shape) != (M, N) or sa.numel() != M or (sb is not None and sb.numel() != N):
+            raise RuntimeError("gemm_nt_f8_emit: shape mismatch")
+    operand = aux
+    if "decode_aux" in unfused:
+        aux = e4m3_to_bf16(aux)
+    if K != Kb:
+        raise RuntimeError(f"{who}: K mismatch {K} vs {Kb}")
+    if fused_q:
+        _chk(out_scale, f32, "out_scale", 1)
+        if out_scale.numel() != M:
+            raise RuntimeError(f"gemm_nt_f8: out_scale has {out_scale.numel()} entries for {M} rows")
+    for name, t, n in (("sa", sa, M), ("sb", sb, N)):
+        if t is not None:
+            _chk(t, f32, name, 1)
+            if t.numel() != n or not t.is_contiguous():
+                raise RuntimeError(f"{who}: {name} must be a contiguous f32 vector of {n} elements")
+    if bias is not None:
+        _chk(bias, f32, "bias", 1)
+    if out is None:
+        out = torch.empty((M, N), device=a.device, dtype=u8 if fused_q else f32 if out_f32 else bf16)
+    ldc = out.stride(0) if M > 1 else N
+    pre8, fused_act = code == EPI_ACT_PRE8, want_act and "act" not in unfused
+    pre = torch.empty((M, N), device=a.device, dtype=u8 if pre8 else bf16) if (want_pre or fused_act) else None
+    if pre8 and ldc != N:
+        raise RuntimeError(f"{who}: want_pre='e4m3' needs a dense output (the copy shares its row stride)")
+    ldaux = 0
+    if aux is not None:
+        _chk(aux, u8 if code == EPI_DACT8 else bf16, "aux", 2)
+        aux, ldaux = _rowmajor(aux)
+    part = torch.empty((M // 128, N), device=a.device, dtype=f32) if fused_q and epi == EPI_DACT else None
+    x8 = torch.empty((M, N), device=a.device, dtype=u8) if fused_emit else None
+    nbytes = (1.0 if f8 else 2.0) * (M * K + N * K) + out.element_size() * M * N + \
+        (float(aux.element_size()) * M * N if aux is not None else 0) + ((1.0 if pre8 else 2.0) * M * N if want_pre else 0)
+    if fused_act:
+        nbytes += 2.0 * M * N
+    if fused_emit:
+        nbytes += 1.0 * M * N
+    tag_epi = "1+pre8" if pre8 else "3,aux8" if code == EPI_DACT8 else f"{epi}{'+pre' if want_pre else ''}"
+    tag_epi += "+act" if fused_act else "+emit" if fused_emit else ""
+    dims = (M, N, K, lda, ldb, ldc, ldaux)
+    with _Timed(who, 2.0 * M * N * K, nbytes, f"{M},{N},{K},epi{tag_epi}{',f32' if out_f32 else ''}{',q8' if fused_q else ''}"):
+        if not f8:
+            lib.call(entry, _p(a), _p(b), _p(out), _p(pre), _p(bias), _p(aux), *dims, float(alpha), code, act,
+                     1 if out_f32 else 0, _stream())
+        elif fused_emit:
+            lib.call(entry, _p(a), _p(b), _p(sa), _p(sb), _p(out), _p(x8), _p(aux), _p(emit), *dims, act, int(fmt_a), _stream())
+        elif fused_q:
+            lib.call(entry, _p(a), _p(b), _p(sa), _p(sb), _p(out), _p(pre), _p(bias), _p(aux), _p(out_scale.contiguous()), _p(part),
+                     *dims, float(alpha), code, act, int(fmt_a), _stream())
+        else:
+            lib.call(entry, _p(a), _p(b), _p(sa), _p(sb), _p(out), _p(pre), _p(bias), _p(aux), *dims, float(alpha), code, act,
+                     int(fmt_a), int(fmt_b), _stream())
+    cs = None
+    if "cast_pre" in unfused:
+        pre = cast_e4m3(pre)
+    if "act" in unfused:
+        pre = activation_fwd(operand, act)
+    if "quantize" in unfused:
+        dense = out
+        out = scale_quantize_rows(dense, out_scale, torch.ones(1, device=out.device, dtype=f32))
+        if want_colsum:
+            cs = colsum(dense)
+    elif fused_q and want_colsum:
+        cs = torch.empty(N, device=a.device, dtype=f32)
+        lib.call("clipa_reduce_partial_rows", _p(part), _p(cs), M // 128, N, _stream())
+    if "emit" in unfused:
+        x8 = scale_quantize_rows(operand, sa, emit, act=act)
+    return out, pre, cs, x8
+
+
+def gemm_nt(a, b, bias=None, *, epi=EPI_NONE, act=ACT_GELU_ERF, aux=None, alpha=1.0, out_f32=False,
+            want_pre=False, out=None, want_act=False):
+    """C[M,N] = epi(alpha * a[M,K] @ b[N,K]^T + bias). a, b bf16; bias f32 [N].
+    want_pre: True -> also the bf16 pre-activation; "e4m3" -> it as saturating e4m3 bytes (uint8 [M,N], the "light8" keep tier:
+    fused into the epilogue on whole-tile shapes, GEMM + cast otherwise).  aux of EPI_DACT may be such a uint8 tensor;
+    want_act (with it): -> (C, act(aux) as bf16 [M,N]) - what activation_fwd(aux, act) returns, written by the epilogue that
+    reads the bytes anyway on whole-tile shapes (by activation_fwd otherwise)."""
+    if want_act and not (epi == EPI_DACT and aux is not None and aux.dtype == u8 and not want_pre and not out_f32):
+        raise RuntimeError("gemm_nt: want_act goes with EPI_DACT on an e4m3 (uint8) second operand")
+    out, pre, _, _ = _gemm_nt("gemm_nt", a, b, bias, epi=epi, act=act, aux=aux, alpha=alpha, out_f32=out_f32, want_pre=want_pre,
+                              out=out, want_act=want_act)
+    return (out, pre) if (want_pre or want_act) else out
+
+
+def gemm_nt_f8(a8, sa, b8, sb, bias=None, *, epi=EPI_NONE, act=ACT_GELU_ERF, aux=None, alpha=1.0, want_pre=False,
+               fmt_a=FMT_E4M3, fmt_b=FMT_E4M3, out_scale=None, want_colsum=False):
+    """C[M,N] bf16 = epi(alpha * sa[m] * sb[n] * a8[M,K] @ b8[N,K]^T + bias); a8, b8 uint8 tensors of fp8 bytes.
+    want_pre: True -> also the bf16 pre-activation; "e4m3" -> it as saturating e4m3 bytes (uint8 [M,N]: fused into the epilogue on
+    whole-tile shapes, GEMM + cast otherwise).  aux of EPI_DACT may be such a uint8 tensor.
+    out_scale (f32 [M]; round 6): the output leaves as e4m3 bytes, row m = the bf16 result times out_scale[m] (the operand of the
+    next GEMM with de-quantisation scale 1 / out_scale: row_bound) - written by the epilogue itself for EPI_ACT and for EPI_DACT
+    from an e4m3 operand on whole-tile shapes, GEMM + scaled quantiser otherwise; want_colsum (EPI_DACT): also the column sums of
+    the unscaled outputs (f32 [N]).  -> q8 [, pre] [, colsum]."""
+    out, pre, cs, _ = _gemm_nt("gemm_nt_f8", a8, b8, bias, sa=sa, sb=sb, epi=epi, act=act, aux=aux, alpha=alpha, want_pre=want_pre,
+                               fmt_a=fmt_a, fmt_b=fmt_b, out_scale=out_scale, want_colsum=want_colsum)
+    res = [out] + ([pre] if want_pre else []) + ([cs] if want_colsum and out_scale is not None else [])
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def gemm_nt_f8_emit(a8, sa, b8, sb, aux8, t, *, act=ACT_GELU_ERF, fmt_a=FMT_E4M3):
+    """EPI_DACT from the kept e4m3 pre-activation that also emits the activation operand of the same layer's fp8 weight gradient:
+    -> (C bf16 [M,N] = gemm_nt_f8(a8, sa, b8, sb, epi=EPI_DACT, aux=aux8), X8 uint8 [M,N] = scale_quantize_rows(aux8, sa, t, act=act)),
+    X8 written by the GEMM's epilogue on whole-tile shapes (clipa_gemm_nt_f8_emit), by the two separate launches otherwise."""
+    out, _, _, x8 = _gemm_nt("gemm_nt_f8", a8, b8, None, sa=sa, sb=sb, epi=EPI_DACT, act=act, aux=aux8, fmt_a=fmt_a, emit=t)
+    return out, x8
 
 
 def cast_e4m3(x):
@@ -129,69 +337,6 @@ def e4m3_to_bf16(x8):
     return out
 
 
-def gemm_nt(a, b, bias=None, *, epi=EPI_NONE, act=ACT_GELU_ERF, aux=None, alpha=1.0, out_f32=False,
-            want_pre=False, out=None, want_act=False):
-    """C[M,N] = epi(alpha * a[M,K] @ b[N,K]^T + bias). a, b bf16; bias f32 [N].
-    want_pre: True -> also the bf16 pre-activation; "e4m3" -> it as saturating e4m3 bytes (uint8 [M,N], the "light8" keep tier:
-    fused into the epilogue on whole-tile shapes, GEMM + cast otherwise).  aux of EPI_DACT may be such a uint8 tensor;
-    want_act (with it): -> (C, act(aux) as bf16 [M,N]) - what activation_fwd(aux, act) returns, written by the epilogue that
-    reads the bytes anyway on whole-tile shapes (by activation_fwd otherwise)."""
-    if want_act:
-        if not (epi == EPI_DACT and aux is not None and aux.dtype == u8 and not want_pre and not out_f32):
-            raise RuntimeError("gemm_nt: want_act goes with EPI_DACT on an e4m3 (uint8) second operand")
-        if not _whole_tiles(a.shape[0], b.shape[0], a.shape[1]) or (out is not None and out.stride(0) != b.shape[0]):
-            return gemm_nt(a, b, bias, epi=epi, act=act, aux=aux, alpha=alpha, out=out), activation_fwd(aux, act)
-    if want_pre == "e4m3" and not (epi == EPI_ACT and not out_f32 and _whole_tiles(a.shape[0], b.shape[0], a.shape[1])):
-        o, pre = gemm_nt(a, b, bias, epi=epi, act=act, aux=aux, alpha=alpha, want_pre=True, out=out)
-        return o, cast_e4m3(pre)
-    if aux is not None and aux.dtype == u8:
-        if epi != EPI_DACT:
-            raise RuntimeError("gemm_nt: an e4m3 (uint8) second operand goes with EPI_DACT only")
-        if not _whole_tiles(a.shape[0], b.shape[0], a.shape[1]):
-            aux = e4m3_to_bf16(aux)
-    _chk(a, bf16, "a", 2)
-    _chk(b, bf16, "b", 2)
-    a, lda = _rowmajor(a)
-    b, ldb = _rowmajor(b)
-    M, K = a.shape
-    N, Kb = b.shape
-    if K != Kb:
-        raise RuntimeError(f"gemm_nt: K mismatch {K} vs {Kb}")
-    if bias is not None:
-        _chk(bias, f32, "bias", 1)
-    if out is None:
-        out = torch.empty((M, N), device=a.device, dtype=f32 if out_f32 else bf16)
-    ldc = out.stride(0) if M > 1 else N
-    pre8 = want_pre == "e4m3"
-    pre = torch.empty((M, N), device=a.device, dtype=u8 if pre8 else bf16) if (want_pre or want_act) else None
-    if pre8 and ldc != N:
-        raise RuntimeError("gemm_nt: want_pre='e4m3' needs a dense output (the copy shares its row stride)")
-    ldaux, aux_sz = 0, 2
-    if aux is not None and aux.dtype == u8:
-        _chk(aux, u8, "aux", 2)
-        aux, ldaux = _rowmajor(aux)
-        epi, aux_sz = EPI_DACT8, 1
-    elif aux is not None:
-        _chk(aux, bf16, "aux", 2)
-        aux, ldaux = _rowmajor(aux)
-    if pre8:
-        epi = EPI_ACT_PRE8
-    osz = 4 if out_f32 else 2
-    nbytes = 2.0 * (M * K + N * K) + osz * M * N + (float(aux_sz) * M * N if aux is not None else 0) + \
-        ((1.0 if pre8 else 2.0) * M * N if want_pre else 0)
-    if want_act:
-        nbytes += 2.0 * M * N
-    tag_epi = {EPI_ACT_PRE8: "1+pre8", EPI_DACT8: "3,aux8+act" if want_act else "3,aux8"}.get(epi, f"{epi}{'+pre' if want_pre else ''}")
-    with _Timed("gemm_nt", 2.0 * M * N * K, nbytes, f"{M},{N},{K},epi{tag_epi}{',f32' if out_f32 else ''}"):
-        lib.call("clipa_gemm_nt", _p(a), _p(b), _p(out), _p(pre), _p(bias), _p(aux), M, N, K, lda, ldb, ldc, ldaux,
-                 float(alpha), epi, act, 1 if out_f32 else 0, _stream())
-    return (out, pre) if (want_pre or want_act) else out
-
-
-FMT_E4M3, FMT_E5M2 = 0, 1
-u8 = torch.uint8
-
-
 def quantize_rows(x, fmt=FMT_E4M3, want_colsum=False, want_rownorm=False):
     """Row-scaled fp8 operand of a bf16 matrix: -> (q uint8 [M,K] holding OCP e4m3 / e5m2 bytes, dq f32 [M]) with
     x[r,:] ~ dq[r] * fp8(q[r,:]).  want_colsum: also sum_r x[r,:] (f32 [K]; the bias gradient when x is a layer's dY);
@@ -206,8 +351,7 @@ def quantize_rows(x, fmt=FMT_E4M3, want_colsum=False, want_rownorm=False):
     if want_colsum:
         cs = torch.empty(K, device=x.device, dtype=f32)
         rn = torch.empty(M, device=x.device, dtype=f32) if want_rownorm else None
-        wsb = lib.query("clipa_quantize_rows_colsum_workspace", M, K)
-        ws = torch.empty(max(wsb, 4) // 4, device=x.device, dtype=f32)
+        ws, wsb = _workspace("clipa_quantize_rows_colsum_workspace", M, K, device=x.device)
         with _Timed("quantize_rows", 0.0, 3.0 * M * K, f"{M},{K},+colsum"):
             lib.call("clipa_quantize_rows_colsum", _p(x), _p(q), _p(dq), _p(cs), _p(rn), M, K, ld, K, int(fmt), _p(ws), wsb, _stream())
         return (q, dq, cs, rn) if want_rownorm else (q, dq, cs)
@@ -232,11 +376,6 @@ def layernorm_fwd_q8(x, gamma, beta, eps=1e-5, want_bf16=False, want_rownorm=Fal
     with _Timed("ln_fwd_q8", 0.0, float(rows) * D * (3 + (2 if want_bf16 else 0)), f"{rows},{D}"):
         lib.call("clipa_layernorm_fwd_q8n", _p(x), _p(gamma), _p(beta), _p(y), _p(q), _p(dq), _p(rn), rows, D, float(eps), _stream())
     return (y, q, dq, rn) if want_rownorm else (y, q, dq)
-
-
-def _whole_tiles_f8(M, N, K):
-    """Shapes the four-wave fp8 GEMM takes (gemm_f8a.hip: f8a_eligible): the fused e4m3 epilogues exist only there."""
-    return M % 256 == 0 and N % 256 == 0 and K % 256 == 0 and K >= 512
 
 
 def row_bound(rownorm, wnorm, bmax=None, factor=1.13):
@@ -268,143 +407,6 @@ def absmax(v):
     out = torch.empty(1, device=v.device, dtype=f32)
     lib.call("clipa_absmax_f32", _p(v.contiguous()), v.numel(), _p(out), _stream())
     return out
-
-
-def gemm_nt_f8_emit(a8, sa, b8, sb, aux8, t, *, act=ACT_GELU_ERF, fmt_a=FMT_E4M3):
-    """EPI_DACT from the kept e4m3 pre-activation that also emits the activation operand of the same layer's fp8 weight gradient:
-    -> (C bf16 [M,N] = gemm_nt_f8(a8, sa, b8, sb, epi=EPI_DACT, aux=aux8), X8 uint8 [M,N] = scale_quantize_rows(aux8, sa, t, act=act)),
-    X8 written by the GEMM's epilogue on whole-tile shapes (clipa_gemm_nt_f8_emit), by the two separate launches otherwise."""
-    M, K = a8.shape
-    N = b8.shape[0]
-    if not (_whole_tiles_f8(M, N, K) and sa is not None):
-        return (gemm_nt_f8(a8, sa, b8, sb, None, epi=EPI_DACT, act=act, aux=aux8, fmt_a=fmt_a),
-                scale_quantize_rows(aux8, sa, t, act=act))
-    _chk(a8, u8, "a8", 2)
-    _chk(b8, u8, "b8", 2)
-    _chk(aux8, u8, "aux8", 2)
-    _chk(sa, f32, "sa", 1)
-    _chk(t, f32, "t")
-    a8, lda = _rowmajor(a8)
-    b8, ldb = _rowmajor(b8)
-    aux8, ldaux = _rowmajor(aux8)
-    if b8.shape[1] != K or tuple(aux8.shape) != (M, N) or sa.numel() != M or (sb is not None and sb.numel() != N):
-        raise RuntimeError("gemm_nt_f8_emit: shape mismatch")
-    out = torch.empty((M, N), device=a8.device, dtype=bf16)
-    x8 = torch.empty((M, N), device=a8.device, dtype=u8)
-    with _Timed("gemm_nt_f8", 2.0 * M * N * K, 1.0 * (M * K + N * K) + 4.0 * M * N, f"{M},{N},{K},epi3,aux8+emit"):
-        lib.call("clipa_gemm_nt_f8_emit", _p(a8), _p(b8), _p(sa), _p(sb), _p(out), _p(x8), _p(aux8), _p(t), M, N, K, lda, ldb, N, ldaux,
-                 act, int(fmt_a), _stream())
-    return out, x8
-
-
-def gemm_nt_f8(a8, sa, b8, sb, bias=None, *, epi=EPI_NONE, act=ACT_GELU_ERF, aux=None, alpha=1.0, want_pre=False,
-               fmt_a=FMT_E4M3, fmt_b=FMT_E4M3, out_scale=None, want_colsum=False):
-    """C[M,N] bf16 = epi(alpha * sa[m] * sb[n] * a8[M,K] @ b8[N,K]^T + bias); a8, b8 uint8 tensors of fp8 bytes.
-    want_pre: True -> also the bf16 pre-activation; "e4m3" -> it as saturating e4m3 bytes (uint8 [M,N]: fused into the epilogue on
-    whole-tile shapes, GEMM + cast otherwise).  aux of EPI_DACT may be such a uint8 tensor.
-    out_scale (f32 [M]; round 6): the output leaves as e4m3 bytes, row m = the bf16 result times out_scale[m] (the operand of the
-    next GEMM with de-quantisation scale 1 / out_scale: row_bound) - written by the epilogue itself for EPI_ACT and for EPI_DACT
-    from an e4m3 operand on whole-tile shapes, GEMM + scaled quantiser otherwise; want_colsum (EPI_DACT): also the column sums of
-    the unscaled outputs (f32 [N]).  -> q8 [, pre] [, colsum]."""
-    whole = _whole_tiles_f8(a8.shape[0], b8.shape[0], a8.shape[1]) and fmt_b == FMT_E4M3
-    if out_scale is not None:
-        fused = whole and ((epi == EPI_ACT and not want_colsum) or (epi == EPI_DACT and aux is not None and aux.dtype == u8 and bias is None))
-        if not fused:
-            r = gemm_nt_f8(a8, sa, b8, sb, bias, epi=epi, act=act, aux=aux, alpha=alpha, want_pre=want_pre, fmt_a=fmt_a, fmt_b=fmt_b)
-            out, pre = r if want_pre else (r, None)
-            ones = torch.ones(1, device=out.device, dtype=f32)
-            res = [scale_quantize_rows(out, out_scale, ones)]
-            if want_pre:
-                res.append(pre)
-            if want_colsum:
-                res.append(colsum(out))
-            return res[0] if len(res) == 1 else tuple(res)
-        return _gemm_nt_f8q(a8, sa, b8, sb, bias, epi, act, aux, alpha, want_pre, fmt_a, out_scale, want_colsum)
-    if want_pre == "e4m3" and not (epi == EPI_ACT and whole):
-        o, pre = gemm_nt_f8(a8, sa, b8, sb, bias, epi=epi, act=act, aux=aux, alpha=alpha, want_pre=True, fmt_a=fmt_a, fmt_b=fmt_b)
-        return o, cast_e4m3(pre)
-    if aux is not None and aux.dtype == u8:
-        if epi != EPI_DACT:
-            raise RuntimeError("gemm_nt_f8: an e4m3 (uint8) second operand goes with EPI_DACT only")
-        if not whole:
-            aux = e4m3_to_bf16(aux)
-    _chk(a8, u8, "a8", 2)
-    _chk(b8, u8, "b8", 2)
-    a8, lda = _rowmajor(a8)
-    b8, ldb = _rowmajor(b8)
-    M, K = a8.shape
-    N, Kb = b8.shape
-    if K != Kb:
-        raise RuntimeError(f"gemm_nt_f8: K mismatch {K} vs {Kb}")
-    for name, t, n in (("sa", sa, M), ("sb", sb, N)):
-        if t is not None:
-            _chk(t, f32, name, 1)
-            if t.numel() != n or not t.is_contiguous():
-                raise RuntimeError(f"gemm_nt_f8: {name} must be a contiguous f32 vector of {n} elements")
-    if bias is not None:
-        _chk(bias, f32, "bias", 1)
-    pre8 = want_pre == "e4m3"
-    out = torch.empty((M, N), device=a8.device, dtype=bf16)
-    pre = torch.empty((M, N), device=a8.device, dtype=u8 if pre8 else bf16) if want_pre else None
-    ldaux, aux_sz = 0, 2
-    if aux is not None and aux.dtype == u8:
-        _chk(aux, u8, "aux", 2)
-        aux, ldaux = _rowmajor(aux)
-        epi, aux_sz = EPI_DACT8, 1
-    elif aux is not None:
-        _chk(aux, bf16, "aux", 2)
-        aux, ldaux = _rowmajor(aux)
-    if pre8:
-        epi = EPI_ACT_PRE8
-    nbytes = 1.0 * (M * K + N * K) + 2.0 * M * N + (float(aux_sz) * M * N if aux is not None else 0) + \
-        ((1.0 if pre8 else 2.0) * M * N if want_pre else 0)
-    tag_epi = {EPI_ACT_PRE8: "1+pre8", EPI_DACT8: "3,aux8"}.get(epi, f"{epi}{'+pre' if want_pre else ''}")
-    with _Timed("gemm_nt_f8", 2.0 * M * N * K, nbytes, f"{M},{N},{K},epi{tag_epi}"):
-        lib.call("clipa_gemm_nt_f8", _p(a8), _p(b8), _p(sa), _p(sb), _p(out), _p(pre), _p(bias), _p(aux), M, N, K, lda, ldb,
-                 N, ldaux, float(alpha), epi, act, int(fmt_a), int(fmt_b), _stream())
-    return (out, pre) if want_pre else out
-
-
-def _gemm_nt_f8q(a8, sa, b8, sb, bias, epi, act, aux, alpha, want_pre, fmt_a, out_scale, want_colsum):
-    """The fused form of gemm_nt_f8(out_scale=...) (clipa_gemm_nt_f8q; whole-tile shapes)."""
-    _chk(a8, u8, "a8", 2)
-    _chk(b8, u8, "b8", 2)
-    _chk(out_scale, f32, "out_scale", 1)
-    a8, lda = _rowmajor(a8)
-    b8, ldb = _rowmajor(b8)
-    M, K = a8.shape
-    N = b8.shape[0]
-    if out_scale.numel() != M:
-        raise RuntimeError(f"gemm_nt_f8: out_scale has {out_scale.numel()} entries for {M} rows")
-    for name, t, n in (("sa", sa, M), ("sb", sb, N)):
-        if t is not None:
-            _chk(t, f32, name, 1)
-            if t.numel() != n or not t.is_contiguous():
-                raise RuntimeError(f"gemm_nt_f8: {name} must be a contiguous f32 vector of {n} elements")
-    q = torch.empty((M, N), device=a8.device, dtype=u8)
-    pre8 = want_pre == "e4m3"
-    pre = torch.empty((M, N), device=a8.device, dtype=u8 if pre8 else bf16) if want_pre else None
-    ldaux, code, part = 0, epi, None
-    if epi == EPI_DACT:
-        _chk(aux, u8, "aux", 2)
-        aux, ldaux = _rowmajor(aux)
-        code = EPI_DACT8
-        part = torch.empty((M // 128, N), device=a8.device, dtype=f32)
-    elif pre8:
-        code = EPI_ACT_PRE8
-    nbytes = 1.0 * (M * K + N * K) + 1.0 * M * N + (1.0 * M * N if aux is not None else 0) + ((1.0 if pre8 else 2.0) * M * N if want_pre else 0)
-    tag = {EPI_ACT_PRE8: "1+pre8", EPI_DACT8: "3,aux8"}.get(code, f"{epi}{'+pre' if want_pre else ''}")
-    with _Timed("gemm_nt_f8", 2.0 * M * N * K, nbytes, f"{M},{N},{K},epi{tag},q8"):
-        lib.call("clipa_gemm_nt_f8q", _p(a8), _p(b8), _p(sa), _p(sb), _p(q), _p(pre), _p(bias), _p(aux), _p(out_scale.contiguous()),
-                 _p(part), M, N, K, lda, ldb, N, ldaux, float(alpha), code, act, int(fmt_a), _stream())
-    res = [q]
-    if want_pre:
-        res.append(pre)
-    if want_colsum:
-        cs = torch.empty(N, device=a8.device, dtype=f32)
-        lib.call("clipa_reduce_partial_rows", _p(part), _p(cs), M // 128, N, _stream())
-        res.append(cs)
-    return res[0] if len(res) == 1 else tuple(res)
 
 
 def rowscale_max(a, b=None):
@@ -471,8 +473,7 @@ def gemm_tn_f8(p8, q8, t=None, alpha=1.0, fmt_p=FMT_E4M3, out_dtype=f32):
         raise RuntimeError(f"gemm_tn_f8: M mismatch {M} vs {M2}")
     if t is not None:
         _chk(t, f32, "t", 1)
-    wsb = lib.query("clipa_gemm_tn_f8_workspace", M, R, C)
-    ws = torch.empty(max(wsb, 4) // 4, device=p8.device, dtype=f32)
+    ws, wsb = _workspace("clipa_gemm_tn_f8_workspace", M, R, C, device=p8.device)
     out = torch.empty((R, C), device=p8.device, dtype=out_dtype)
     with _Timed("gemm_tn_f8", 2.0 * M * R * C, 1.0 * M * (R + C) + out.element_size() * R * C, f"{M},{R},{C}"):
         lib.call("clipa_gemm_tn_f8", _p(p8), _p(q8), _p(out), M, R, C, ldp, ldq, float(alpha), _p(t), int(fmt_p),
@@ -491,9 +492,7 @@ def gemm_tn(p, q, out_dtype=f32, want_colsum=False):
     M2, C = q.shape
     if M != M2:
         raise RuntimeError(f"gemm_tn: M mismatch {M} vs {M2}")
-    ns = ctypes.c_int64(0)
-    wsb = lib.query("clipa_gemm_tn_workspace", M, R, C, ctypes.byref(ns))
-    ws = torch.empty(max(wsb, 4) // 4, device=p.device, dtype=f32)
+    ws, wsb = _workspace("clipa_gemm_tn_workspace", M, R, C, ctypes.byref(ctypes.c_int64(0)), device=p.device)
     out = torch.empty((R, C), device=p.device, dtype=out_dtype)
     cs = torch.empty(R, device=p.device, dtype=f32) if want_colsum else None
     with _Timed("gemm_tn", 2.0 * M * R * C, 2.0 * M * (R + C) + out.element_size() * R * C, f"{M},{R},{C}"):
@@ -523,88 +522,80 @@ def layernorm_bwd(x, gamma, dy, dres=None, eps=1e-5, beta=None, q8_fmt=None, wan
     [, want_rownorm=True]) - the fp8 operand of the linear layer this gradient reaches next, from the same pass."""
     x = x.contiguous()
     dy = dy.contiguous()
+    if dres is not None:
+        dres = dres.contiguous()
     D = x.shape[-1]
     rows = x.numel() // D
-    if q8_fmt is not None:
+    q8 = q8_fmt is not None
+    if q8:
         _chk(x, bf16, "x")
         _chk(dy, bf16, "dy")
         if dres is not None:
-            dres = dres.contiguous()
             _chk(dres, bf16, "dres")
-        wsb = lib.query("clipa_layernorm_bwd_q8_workspace", rows, D)
-        ws = torch.empty(max(wsb, 4) // 4, device=x.device, dtype=f32)
-        dx = torch.empty_like(x)
-        dgamma = torch.empty(D, device=x.device, dtype=f32)
-        dbeta = torch.empty(D, device=x.device, dtype=f32)
+    ws, wsb = _workspace("clipa_layernorm_bwd_q8_workspace" if q8 else "clipa_layernorm_bwd_workspace", rows, D, device=x.device)
+    dx = torch.empty_like(x)
+    dgamma = torch.empty(D, device=x.device, dtype=f32)
+    dbeta = torch.empty(D, device=x.device, dtype=f32)
+    if not q8 and dres is not None and dres.dtype != x.dtype:
+        raise RuntimeError("layernorm_bwd: dres dtype must match x")
+    y = None
+    if beta is not None:
+        _chk(beta, f32, "beta", 1)
+        y = torch.empty(x.shape, device=x.device, dtype=dy.dtype)
+    res = (dx, dgamma, dbeta) if y is None else (dx, dgamma, dbeta, y)
+    if q8:
         q = torch.empty((rows, D), device=x.device, dtype=u8)
         dq = torch.empty(rows, device=x.device, dtype=f32)
         cs = torch.empty(D, device=x.device, dtype=f32)
         rn = torch.empty(rows, device=x.device, dtype=f32) if want_rownorm else None
-        y = None
-        if beta is not None:
-            _chk(beta, f32, "beta", 1)
-            y = torch.empty(x.shape, device=x.device, dtype=bf16)
         nbytes = float(rows) * D * (7 + (2 if dres is not None else 0) + (2 if y is not None else 0))
         with _Timed("ln_bwd", 0.0, nbytes, f"{rows},{D},+q8{',+y' if y is not None else ''}"):
             lib.call("clipa_layernorm_bwd_q8", _p(x), _p(gamma), _p(beta), _p(dy), _p(dres), _p(dx), _p(y), _p(q), _p(dq), _p(cs), _p(rn),
                      _p(dgamma), _p(dbeta), rows, D, float(eps), int(q8_fmt), _p(ws), wsb, _stream())
-        q8 = (q, dq, cs, rn) if want_rownorm else (q, dq, cs)
-        return (dx, dgamma, dbeta, y, q8) if y is not None else (dx, dgamma, dbeta, q8)
-    wsb = lib.query("clipa_layernorm_bwd_workspace", rows, D)
-    ws = torch.empty(max(wsb, 4) // 4, device=x.device, dtype=f32)
-    dx = torch.empty_like(x)
-    dgamma = torch.empty(D, device=x.device, dtype=f32)
-    dbeta = torch.empty(D, device=x.device, dtype=f32)
-    if dres is not None:
-        dres = dres.contiguous()
-        if dres.dtype != x.dtype:
-            raise RuntimeError("layernorm_bwd: dres dtype must match x")
+        return res + ((q, dq, cs, rn) if want_rownorm else (q, dq, cs),)
     nbytes = float(rows) * D * (2 * x.element_size() + dy.element_size() + (x.element_size() if dres is not None else 0))
-    if beta is not None:
-        _chk(beta, f32, "beta", 1)
-        y = torch.empty(x.shape, device=x.device, dtype=dy.dtype)
+    tail = (rows, D, float(eps), int(x.dtype == f32), int(dy.dtype == f32), _p(ws), wsb, _stream())
+    if y is not None:
         with _Timed("ln_bwd", 0.0, nbytes + float(rows) * D * y.element_size(), f"{rows},{D},+y"):
-            lib.call("clipa_layernorm_bwd_y", _p(x), _p(gamma), _p(beta), _p(dy), _p(dres), _p(dx), _p(y), _p(dgamma), _p(dbeta),
-                     rows, D, float(eps), int(x.dtype == f32), int(dy.dtype == f32), _p(ws), wsb, _stream())
-        return dx, dgamma, dbeta, y
-    with _Timed("ln_bwd", 0.0, nbytes, f"{rows},{D}"):
-        lib.call("clipa_layernorm_bwd", _p(x), _p(gamma), _p(dy), _p(dres), _p(dx), _p(dgamma), _p(dbeta), rows, D,
-                 float(eps), int(x.dtype == f32), int(dy.dtype == f32), _p(ws), wsb, _stream())
-    return dx, dgamma, dbeta
+            lib.call("clipa_layernorm_bwd_y", _p(x), _p(gamma), _p(beta), _p(dy), _p(dres), _p(dx), _p(y), _p(dgamma), _p(dbeta), *tail)
+    else:
+        with _Timed("ln_bwd", 0.0, nbytes, f"{rows},{D}"):
+            lib.call("clipa_layernorm_bwd", _p(x), _p(gamma), _p(dy), _p(dres), _p(dx), _p(dgamma), _p(dbeta), *tail)
+    return res
+
+
+def _attention(name, qkv, H, causal, pairs, tag):
+    """What the four attention wrappers share: -> (D, head dim, softmax scale, the launch's profiler record).  pairs = the
+    (query, key) pairs of one head: 4 FLOPs per pair and head-dim element forward, 10 backward, half of them under a causal mask."""
+    _chk(qkv, bf16, "qkv", 2)
+    D = qkv.shape[1] // 3
+    dh = D // H
+    work = (4.0 if name == "attention_fwd" else 10.0) * H * pairs * dh * (0.5 if causal else 1.0)
+    return D, dh, 1.0 / math.sqrt(dh), _Timed(name, work, 0.0, f"{tag},dh{dh}")
 
 
 def attention_fwd(qkv, B, L, H, causal, want_stats=False):
     """qkv [B*L, 3*H*64] bf16 (q | k | v column blocks) -> out [B*L, H*64] bf16 (+ softmax statistics
     f32 [B*H*L, 2] for the backward when want_stats)."""
-    _chk(qkv, bf16, "qkv", 2)
-    D = qkv.shape[1] // 3
-    dh = D // H
+    D, dh, sm_scale, timed = _attention("attention_fwd", qkv, H, causal, B * L * L, f"B{B},H{H},L{L}")
     out = torch.empty((B * L, D), device=qkv.device, dtype=bf16)
-    base = qkv.data_ptr()
-    ld = qkv.stride(0)
     stats = torch.empty((B * H * L, 2), device=qkv.device, dtype=f32) if want_stats else None
-    with _Timed("attention_fwd", 4.0 * B * H * L * L * dh * (0.5 if causal else 1.0), 0.0, f"B{B},H{H},L{L},dh{dh}"):
-        lib.call("clipa_attention_fwd", ctypes.c_void_p(base), ctypes.c_void_p(base + 2 * D),
-                 ctypes.c_void_p(base + 4 * D), _p(out), _p(stats), B, H, L, dh, ld, D, 1.0 / math.sqrt(dh), int(causal),
+    with timed:
+        lib.call("clipa_attention_fwd", *_qkv_ptrs(qkv, D), _p(out), _p(stats), B, H, L, dh, qkv.stride(0), D, sm_scale, int(causal),
                  _stream())
     return (out, stats) if want_stats else out
 
 
 def attention_bwd(qkv, out, dout, stats, B, L, H, causal):
-    _chk(qkv, bf16, "qkv", 2)
+    D, dh, sm_scale, timed = _attention("attention_bwd", qkv, H, causal, B * L * L, f"B{B},H{H},L{L}")
     _chk(stats, f32, "stats", 2)
     _chk(out, bf16, "out", 2)
     _chk(dout, bf16, "dout", 2)
     dout = dout.contiguous()
-    D = qkv.shape[1] // 3
-    dh = D // H
     dqkv = torch.empty_like(qkv)
-    base, dbase = qkv.data_ptr(), dqkv.data_ptr()
-    with _Timed("attention_bwd", 10.0 * B * H * L * L * dh * (0.5 if causal else 1.0), 0.0, f"B{B},H{H},L{L},dh{dh}"):
-        lib.call("clipa_attention_bwd", ctypes.c_void_p(base), ctypes.c_void_p(base + 2 * D),
-                 ctypes.c_void_p(base + 4 * D), _p(out), _p(dout), _p(stats), ctypes.c_void_p(dbase), ctypes.c_void_p(dbase + 2 * D),
-                 ctypes.c_void_p(dbase + 4 * D), B, H, L, dh, qkv.stride(0), D, dqkv.stride(0), 1.0 / math.sqrt(dh),
-                 int(causal), _stream())
+    with timed:
+        lib.call("clipa_attention_bwd", *_qkv_ptrs(qkv, D), _p(out), _p(dout), _p(stats), *_qkv_ptrs(dqkv, D), B, H, L, dh,
+                 qkv.stride(0), D, dqkv.stride(0), sm_scale, int(causal), _stream())
     return dqkv
 
 
@@ -637,33 +628,25 @@ class VarLen:
 
 def attention_fwd_varlen(qkv, vl, H, causal, want_stats=False):
     """attention_fwd on packed sequences: qkv [vl.rows, 3D] -> out [vl.rows, D] (pad rows zero) (+ statistics [vl.rows * H, 2])."""
-    _chk(qkv, bf16, "qkv", 2)
-    D = qkv.shape[1] // 3
-    dh = D // H
+    D, dh, sm_scale, timed = _attention("attention_fwd", qkv, H, causal, vl.sum_len2, f"varlen{vl.B},H{H},T{vl.T}")
     out = torch.zeros((vl.rows, D), device=qkv.device, dtype=bf16)
     stats = torch.empty((vl.rows * H, 2), device=qkv.device, dtype=f32)
-    base, ld = qkv.data_ptr(), qkv.stride(0)
-    with _Timed("attention_fwd", 4.0 * H * vl.sum_len2 * dh * (0.5 if causal else 1.0), 0.0, f"varlen{vl.B},H{H},T{vl.T},dh{dh}"):
+    with timed:
         for tiles, ids, n in vl.classes:
-            lib.call("clipa_attention_fwd_varlen", ctypes.c_void_p(base), ctypes.c_void_p(base + 2 * D), ctypes.c_void_p(base + 4 * D),
-                     _p(out), _p(stats), _p(vl.seq_start), _p(vl.seq_len), _p(ids), n, tiles, H, dh, ld, D, 1.0 / math.sqrt(dh),
-                     int(causal), _stream())
+            lib.call("clipa_attention_fwd_varlen", *_qkv_ptrs(qkv, D), _p(out), _p(stats), _p(vl.seq_start), _p(vl.seq_len), _p(ids),
+                     n, tiles, H, dh, qkv.stride(0), D, sm_scale, int(causal), _stream())
     return (out, stats) if want_stats else out
 
 
 def attention_bwd_varlen(qkv, out, dout, stats, vl, H, causal):
-    _chk(qkv, bf16, "qkv", 2)
+    D, dh, sm_scale, timed = _attention("attention_bwd", qkv, H, causal, vl.sum_len2, f"varlen{vl.B},H{H},T{vl.T}")
     _chk(stats, f32, "stats", 2)
     dout = dout.contiguous()
-    D = qkv.shape[1] // 3
-    dh = D // H
     dqkv = torch.zeros_like(qkv)                                   # pad rows belong to no sequence: their gradient is zero
-    base, dbase = qkv.data_ptr(), dqkv.data_ptr()
-    with _Timed("attention_bwd", 10.0 * H * vl.sum_len2 * dh * (0.5 if causal else 1.0), 0.0, f"varlen{vl.B},H{H},T{vl.T},dh{dh}"):
+    with timed:
         for tiles, ids, n in vl.classes:
-            lib.call("clipa_attention_bwd_varlen", ctypes.c_void_p(base), ctypes.c_void_p(base + 2 * D), ctypes.c_void_p(base + 4 * D),
-                     _p(out), _p(dout), _p(stats), ctypes.c_void_p(dbase), ctypes.c_void_p(dbase + 2 * D), ctypes.c_void_p(dbase + 4 * D),
-                     _p(vl.seq_start), _p(vl.seq_len), _p(ids), n, tiles, H, dh, qkv.stride(0), D, dqkv.stride(0), 1.0 / math.sqrt(dh),
+            lib.call("clipa_attention_bwd_varlen", *_qkv_ptrs(qkv, D), _p(out), _p(dout), _p(stats), *_qkv_ptrs(dqkv, D),
+                     _p(vl.seq_start), _p(vl.seq_len), _p(ids), n, tiles, H, dh, qkv.stride(0), D, dqkv.stride(0), sm_scale,
                      int(causal), _stream())
     return dqkv
 
@@ -711,8 +694,7 @@ def resized_crop_u8(src, boxes, size, gray_flags=None):
             raise RuntimeError("resized_crop_u8: gray_flags must have one byte per sample")
     check_token_ids()                                   # surfaces an earlier launch's rejected samples
     out = torch.empty((B, size, size, 3), device=src.device, dtype=u8)
-    wsb = lib.query("clipa_resized_crop_workspace", B, Hs, size)
-    ws = torch.empty(wsb, device=src.device, dtype=u8)
+    ws, wsb = _workspace("clipa_resized_crop_workspace", B, Hs, size, device=src.device, dtype=u8, floor=0)
     err = _oob_counter(src.device)
     with _Timed("resized_crop", 0.0, 3.0 * B * (Hs * Ws + Hs * size * 2 + size * size)):
         lib.call("clipa_resized_crop_u8", _p(src), _p(boxes), _p(gray_flags), _p(out), B, Hs, Ws, size, _p(ws), wsb, _p(err),
@@ -757,17 +739,9 @@ def assemble_tokens_bwd(dtok, B, L, need_pos=True):
     dpatch = torch.empty((B * (L - 1), D), device=dtok.device, dtype=bf16)
     dcls = torch.empty(D, device=dtok.device, dtype=f32)
     dpos = torch.empty((L, D), device=dtok.device, dtype=f32) if need_pos else None
-    wsb = lib.query("clipa_assemble_tokens_bwd_workspace", B, L, D)
-    ws = torch.empty(max(wsb, 4) // 4, device=dtok.device, dtype=f32)
+    ws, wsb = _workspace("clipa_assemble_tokens_bwd_workspace", B, L, D, device=dtok.device)
     lib.call("clipa_assemble_tokens_bwd", _p(dtok), _p(dpatch), _p(dcls), _p(dpos), B, L, D, _p(ws), wsb, _stream())
     return dpatch, dcls, dpos
-
-
-# Out-of-range token ids: nn.Embedding raises; the kernels count them into a device int32 instead of clamping silently.
-# The count is fetched without stalling the stream (pinned buffer + event) and checked at the next embedding call or by
-# `check_token_ids()`: a bad id surfaces as a RuntimeError at most one step late.
-_OOB_PENDING = []
-_OOB_LOCK = threading.Lock()      # appended to from the autograd thread (embed_tokens_bwd), drained from the main thread
 
 
 def _oob_counter(device):
@@ -827,8 +801,8 @@ def embed_tokens_bwd(ids, dx, vocab, need_table=True, need_pos=True):
     dtable = torch.empty((vocab, D), device=dx.device, dtype=f32) if need_table else None
     dpos = torch.empty((T, D), device=dx.device, dtype=f32) if need_pos else None
     oob = _oob_counter(ids.device)
-    wsb = lib.query("clipa_embed_tokens_bwd_workspace", B, T, D, vocab, int(need_table), int(need_pos))
-    ws = torch.empty(max(wsb, 8) // 8, device=dx.device, dtype=torch.int64)
+    ws, wsb = _workspace("clipa_embed_tokens_bwd_workspace", B, T, D, vocab, int(need_table), int(need_pos), device=dx.device,
+                         dtype=torch.int64, floor=8)
     lib.call("clipa_embed_tokens_bwd", _p(ids), _p(dx), _p(dtable), _p(dpos), B, T, D, vocab, _p(oob), _p(ws), wsb, _stream())
     _oob_submit(oob, "embed_tokens_bwd")
     return dtable, dpos
@@ -899,8 +873,7 @@ def colsum(dy):
     _chk(dy, bf16, "dy", 2)
     dy, ld = _rowmajor(dy)
     M, N = dy.shape
-    wsb = lib.query("clipa_colsum_workspace", M, N)
-    ws = torch.empty(max(wsb, 4) // 4, device=dy.device, dtype=f32)
+    ws, wsb = _workspace("clipa_colsum_workspace", M, N, device=dy.device)
     out = torch.empty(N, device=dy.device, dtype=f32)
     lib.call("clipa_colsum", _p(dy), _p(out), M, N, ld, _p(ws), wsb, _stream())
     return out
@@ -965,8 +938,7 @@ def simce(rows, cols, n_valid, label0, gscale, scale=None, want_grad=True):
     if scale is not None:
         _chk(scale, f32, "scale")
     n8 = (n_valid + 7) // 8 * 8
-    wsb = lib.query("clipa_simce_workspace", R, n_valid)
-    ws = torch.empty(max(wsb, 4) // 4, device=rows.device, dtype=f32)
+    ws, wsb = _workspace("clipa_simce_workspace", R, n_valid, device=rows.device)
     lse = torch.empty(R, device=rows.device, dtype=f32)
     loss_rows = torch.empty(R, device=rows.device, dtype=f32)
     with _Timed("simce", 2.0 * R * n_valid * E * (2 if want_grad else 1)):
@@ -1010,8 +982,7 @@ def simce_distill(rows_s, cols_s, rows_t, cols_t, n_valid, label0, scale_s=None,
     two feed simce_distill_bwd).  Neither logit matrix exists in HBM."""
     ops4, (R, Es, Et, ldas, ldbs, ldat, ldbt) = _distill_operands(rows_s, cols_s, rows_t, cols_t, n_valid, scale_s, scale_t)
     dev = ops4[0].device
-    wsb = lib.query("clipa_simce_distill_workspace", R, n_valid)
-    ws = torch.empty(max(wsb, 4) // 4, device=dev, dtype=f32)
+    ws, wsb = _workspace("clipa_simce_distill_workspace", R, n_valid, device=dev)
     lse_s, lse_t, ce_rows, dist_rows = (torch.empty(R, device=dev, dtype=f32) for _ in range(4))
     with _Timed("simce_distill", 2.0 * R * n_valid * (Es + Et)):
         lib.call("clipa_simce_distill_fwd", *(_p(t) for t in ops4), R, n_valid, Es, Et, ldas, ldbs, ldat, ldbt, _p(scale_s),
@@ -1030,8 +1001,7 @@ def simce_distill_bwd(rows_s, cols_s, rows_t, cols_t, n_valid, label0, gscale, l
                                                                    (g_d, "g_d")))
     dev = ops4[0].device
     n8 = (n_valid + 7) // 8 * 8
-    wsb = lib.query("clipa_simce_distill_workspace", R, n_valid)
-    ws = torch.empty(max(wsb, 4) // 4, device=dev, dtype=f32)
+    ws, wsb = _workspace("clipa_simce_distill_workspace", R, n_valid, device=dev)
     dl = torch.empty((R, n8), device=dev, dtype=bf16)
     dscale_rows = torch.empty(R, device=dev, dtype=f32)
     with _Timed("simce_distill_bwd", 2.0 * R * n_valid * (Es + Et)):
@@ -1051,19 +1021,12 @@ def retrieval_ranks(img, txt, scale=None):
     _chk(txt, f32, "txt", 2)
     if img.shape != txt.shape:
         raise RuntimeError(f"retrieval_ranks: img {tuple(img.shape)} and txt {tuple(txt.shape)} must be the same [N, E]")
-    img, lda = _rowmajor(img)
-    txt, ldb = _rowmajor(txt)
-    if lda % 4 or img.data_ptr() % 16:
-        img, lda = _pad_cols4(img)
-    if ldb % 4 or txt.data_ptr() % 16:
-        txt, ldb = _pad_cols4(txt)
+    img, lda = _aligned_rows(img)
+    txt, ldb = _aligned_rows(txt)
     N, E = img.shape
-    if scale is not None:
-        _chk(scale, f32, "scale")
-        scale = scale.reshape(1).contiguous()
+    scale = _scalar1(scale)
     dev = img.device
-    wsb = lib.query("clipa_retrieval_ranks_workspace", N)
-    ws = torch.empty(max(wsb, 16) // 4, device=dev, dtype=f32)
+    ws, wsb = _workspace("clipa_retrieval_ranks_workspace", N, device=dev, floor=16)
     out = torch.empty((4, (N + 3) // 4 * 4), device=dev, dtype=torch.int32)       # rows 16-byte aligned
     with _Timed("retrieval_ranks", 2.0 * N * N * E):
         lib.call("clipa_retrieval_ranks", _p(img), _p(txt), N, E, lda, ldb, _p(scale), *(_p(out[k]) for k in range(4)), _p(ws),
@@ -1100,19 +1063,12 @@ def retrieval_ranks_multi(img, txt, txt2img, scale=None):
         order = torch.argsort(c, stable=True)
         txt, c = txt.index_select(0, order), c[order]
     c = c.to(torch.int32)                                  # a fresh, 16-byte aligned buffer
-    img, lda = _rowmajor(img)
-    txt, ldb = _rowmajor(txt)
-    if lda % 4 or img.data_ptr() % 16:
-        img, lda = _pad_cols4(img)
-    if ldb % 4 or txt.data_ptr() % 16:
-        txt, ldb = _pad_cols4(txt)
+    img, lda = _aligned_rows(img)
+    txt, ldb = _aligned_rows(txt)
     E = img.shape[1]
-    if scale is not None:
-        _chk(scale, f32, "scale")
-        scale = scale.reshape(1).contiguous()
+    scale = _scalar1(scale)
     dev = img.device
-    wsb = lib.query("clipa_retrieval_ranks_multi_workspace", Ni, Nt)
-    ws = torch.empty(max(wsb, 16) // 4, device=dev, dtype=f32)
+    ws, wsb = _workspace("clipa_retrieval_ranks_multi_workspace", Ni, Nt, device=dev, floor=16)
     oi = torch.empty((2, (Ni + 3) // 4 * 4), device=dev, dtype=torch.int32)       # rows 16-byte aligned
     ot = torch.empty((2, (Nt + 3) // 4 * 4), device=dev, dtype=torch.int32)
     with _Timed("retrieval_ranks_multi", 2.0 * Ni * Nt * E):
@@ -1122,15 +1078,6 @@ def retrieval_ranks_multi(img, txt, txt2img, scale=None):
     if order is not None:
         t2i_gt, t2i_eq = (torch.empty_like(t).index_copy_(0, order, t) for t in (t2i_gt, t2i_eq))
     return oi[0, :Ni], oi[1, :Ni], t2i_gt, t2i_eq
-
-
-def _pad_cols4(x):
-    """[N, E] -> (a [N, E] view of a fresh [N, E rounded up to 4] buffer, its row stride): the kernel wants 16-byte
-    aligned rows."""
-    n, e = x.shape
-    buf = torch.empty((n, (e + 3) // 4 * 4), device=x.device, dtype=x.dtype)
-    buf[:, :e] = x
-    return buf[:, :e], buf.shape[1]
 
 
 def sum_scale(x, scale, out=None, accumulate=False):
@@ -1173,12 +1120,9 @@ def adamw_multi_(params, grads, exp_avgs, exp_avg_sqs, *, lr, beta1, beta2, eps,
         _chk_moments(t, m, v)
     if grad_scale_dev is not None:
         _chk(grad_scale_dev, f32, "grad_scale_dev")
-    arr = ctypes.c_void_p * n
-    cnt = (ctypes.c_int64 * n)(*[t.numel() for t in params])
-    lib.call("clipa_adamw_multi", arr(*[t.data_ptr() for t in params]), arr(*[t.data_ptr() for t in grads]),
-             arr(*[t.data_ptr() for t in exp_avgs]), arr(*[t.data_ptr() for t in exp_avg_sqs]), cnt, n, int(pf32),
-             int(gf32), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
-             float(grad_scale), _p(grad_scale_dev), int(clamp_index), float(clamp[0]), float(clamp[1]), _stream())
+    lib.call("clipa_adamw_multi", _ptr_array(params), _ptr_array(grads), _ptr_array(exp_avgs), _ptr_array(exp_avg_sqs),
+             _numel_array(params), n, int(pf32), int(gf32), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+             int(step), float(grad_scale), _p(grad_scale_dev), int(clamp_index), float(clamp[0]), float(clamp[1]), _stream())
 
 
 def grad_sqnorm(grads, buf=None):
@@ -1193,12 +1137,9 @@ def grad_sqnorm(grads, buf=None):
         for g in sel:
             if g.dtype not in (f32, bf16) or not g.is_contiguous() or not g.is_cuda:
                 raise RuntimeError("grad_sqnorm: gradients must be contiguous f32 / bf16 GPU tensors")
-        n = len(sel)
-        arr = ctypes.c_void_p * n
-        cnt = (ctypes.c_int64 * n)(*[g.numel() for g in sel])
         nblk = sum((g.numel() + 4095) // 4096 for g in sel)            # one partial per 4096-element block, summed in a fixed order
         part = torch.empty(max(nblk, 1), device=dev, dtype=f32)
-        lib.call("clipa_grad_sqnorm_multi", arr(*[g.data_ptr() for g in sel]), cnt, n, int(is32), _p(buf), _p(part), nblk, _stream())
+        lib.call("clipa_grad_sqnorm_multi", _ptr_array(sel), _numel_array(sel), len(sel), int(is32), _p(buf), _p(part), nblk, _stream())
     return buf
 
 

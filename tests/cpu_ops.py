@@ -5,12 +5,11 @@ import math
 
 import torch
 
+from clipa_amd.ops import (ACT_GELU_ERF, ACT_GELU_TANH, ACT_QUICK_GELU, DT_BF16, DT_F32, DT_U8,  # noqa: F401  (re-exported)
+                           EPI_ACT, EPI_ADD, EPI_DACT, EPI_NONE, FMT_E4M3, FMT_E5M2, POOL_FIRST, POOL_INDEX, POOL_LAST,
+                           POOL_MEAN_ALL, POOL_MEAN_PATCH)
 from oracle import clip_oracle as O
 
-EPI_NONE, EPI_ACT, EPI_ADD, EPI_DACT = 0, 1, 2, 3
-ACT_GELU_ERF, ACT_GELU_TANH, ACT_QUICK_GELU = 0, 1, 2
-DT_U8, DT_BF16, DT_F32 = 0, 1, 2
-POOL_FIRST, POOL_LAST, POOL_INDEX, POOL_MEAN_ALL, POOL_MEAN_PATCH = 0, 1, 2, 3, 4
 bf16, f32 = torch.bfloat16, torch.float32
 _ACT = {0: "gelu_erf", 1: "gelu_tanh", 2: "quick_gelu"}
 
@@ -55,7 +54,6 @@ def gemm_nt(a, b, bias=None, *, epi=EPI_NONE, act=0, aux=None, alpha=1.0, out_f3
     return (v, pre) if want_pre else v
 
 
-FMT_E4M3, FMT_E5M2 = 0, 1
 u8 = torch.uint8
 _F8 = {0: (torch.float8_e4m3fn, 448.0), 1: (torch.float8_e5m2, 57344.0)}
 
