@@ -1,13 +1,14 @@
 """clipa_amd - MI355X-native compute engine for the CLIPA / open_clip training step.
 
 Public surface mirrors `open_clip` (clipa_torch/open_clip/__init__.py) for the ViT-CLIP hot path:
-create_model, create_model_and_transforms, create_loss, CLIP, ClipLoss, DistillClipLoss, convert_weights_to_lp,
+create_model, create_model_and_transforms, create_loss, CLIP, ClipLoss, DistillClipLoss, SigLipLoss,
+convert_weights_to_lp,
 get_cast_dtype, list_models, add_model_config; and the trainer's validation (training/train.py: evaluate,
 get_clip_metrics) and multi-caption image-text retrieval (`image_text_retrieval`, `evaluate_retrieval`).
 """
 from .configs import add_model_config, get_model_config, list_models
 from .factory import (create_loss, create_model, create_model_and_transforms, get_cast_dtype, load_checkpoint)
-from .loss import ClipLoss, DistillClipLoss
+from .loss import ClipLoss, DistillClipLoss, SigLipLoss
 from .model import (CLIP, CLIPTextCfg, CLIPVisionCfg, OPENAI_DATASET_MEAN, OPENAI_DATASET_STD, convert_weights_to_lp,
                     get_2d_sincos_pos_embed, resize_pos_embed, resize_text_pos_embed)
 

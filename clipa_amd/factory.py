@@ -13,7 +13,7 @@ from typing import Optional, Tuple, Union
 import torch
 
 from . import configs
-from .loss import ClipLoss, DistillClipLoss
+from .loss import ClipLoss, DistillClipLoss, SigLipLoss
 from .model import (CLIP, OPENAI_DATASET_MEAN, OPENAI_DATASET_STD, convert_weights_to_lp, resize_pos_embed,
                     resize_text_pos_embed)
 
@@ -61,6 +61,8 @@ def create_model(
         pos_embed: str = None,
         interpolation: str = 'bicubic',
         square_resize_only: bool = False,
+        init_logit_scale: Optional[float] = None,
+        init_logit_bias: Optional[float] = None,
 ):
     model_name = model_name.replace('/', '-')
     if isinstance(device, str):
@@ -78,6 +80,11 @@ def create_model(
         model_cfg["vision_cfg"]["image_size"] = force_image_size          # factory.py:186-188
     if pos_embed is not None:
         model_cfg["vision_cfg"]["pos_embed"] = pos_embed                  # factory.py:190-192
+    # SigLIP: these override the config's top-level keys of the same names (a config may carry them too)
+    if init_logit_scale is not None:
+        model_cfg["init_logit_scale"] = init_logit_scale
+    if init_logit_bias is not None:
+        model_cfg["init_logit_bias"] = init_logit_bias
     cast_dtype = get_cast_dtype(precision)
     model = CLIP(**model_cfg, cast_dtype=cast_dtype)
     if pretrained:
@@ -104,10 +111,13 @@ def create_model(
 
 
 def create_loss(args, model=None):
-    """factory.py:262-290 (ClipLoss and DistillClipLoss branches; CoCa is out of scope).  `model` (optional, engine
-    extension): bind the loss to the model so that the image-feature all-gather starts under the text tower (ClipLoss.bind)."""
+    """factory.py:262-290 (ClipLoss and DistillClipLoss branches; CoCa is out of scope), plus upstream open_clip's `--siglip`
+    branch (SigLipLoss).  `model` (optional, engine extension): bind the loss to the model so that the image-feature
+    all-gather starts under the text tower (ClipLoss.bind); SigLipLoss gathers nothing early, so it is not bound."""
     if "coca" in getattr(args, "model", "").lower() and not getattr(args, "distill", False):
         raise NotImplementedError("clipa_amd.create_loss: CoCa losses are out of scope")
+    if getattr(args, "siglip", False) and not getattr(args, "distill", False):
+        return SigLipLoss(rank=args.rank, world_size=args.world_size, use_horovod=getattr(args, "horovod", False))
     cls = DistillClipLoss if getattr(args, "distill", False) else ClipLoss
     loss = cls(
         local_loss=args.local_loss,
@@ -130,7 +140,8 @@ def create_model_and_transforms(model_name: str, pretrained: Optional[str] = Non
                                 image_std: Optional[Tuple[float, ...]] = None, aug_cfg=None,
                                 cache_dir: Optional[str] = None, output_dict: Optional[bool] = None,
                                 to_float_on_device: bool = False, pos_embed: str = None,
-                                interpolation: str = 'bicubic', square_resize_only: bool = False):
+                                interpolation: str = 'bicubic', square_resize_only: bool = False,
+                                init_logit_scale: Optional[float] = None, init_logit_bias: Optional[float] = None):
     """Same signature and return value as factory.py:293-352: (model, preprocess_train, preprocess_val).  The transforms are
     clipa_amd.transform.image_transform - the reference's open_clip/transform.py:91-214 restated on Pillow alone (torchvision,
     which the reference builds them from, is not part of this image); they run on the host in the loader workers exactly like
@@ -140,7 +151,8 @@ def create_model_and_transforms(model_name: str, pretrained: Optional[str] = Non
                          force_patch_dropout=force_patch_dropout, force_image_size=force_image_size,
                          pretrained_image=pretrained_image, pretrained_hf=pretrained_hf, cache_dir=cache_dir,
                          output_dict=output_dict, pos_embed=pos_embed, interpolation=interpolation,
-                         square_resize_only=square_resize_only)
+                         square_resize_only=square_resize_only, init_logit_scale=init_logit_scale,
+                         init_logit_bias=init_logit_bias)
     if image_mean is not None:
         model.visual.image_mean = image_mean
     if image_std is not None:

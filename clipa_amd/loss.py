@@ -372,3 +372,87 @@ class DistillClipLoss(ClipLoss):
         if output_dict:
             return {"contrastive_loss": contrastive, "distill_loss": distill}
         return contrastive, distill
+
+
+class SigLipLossFn(torch.autograd.Function):
+    """sum_ij -logsigmoid(y_ij (s I . T_all^T + b)_ij) / B over this rank's B images and all W*B texts, y = +1 at column
+    B * rank + i and -1 elsewhere.  s = exp(logit_scale) as the model returns it, b = logit_bias."""
+
+    @staticmethod
+    def forward(ctx, img, txt, logit_scale, logit_bias, rank, world_size, group):
+        B, E = img.shape
+        s_dev = logit_scale.detach().to(f32).reshape(1).contiguous()     # stay on the device
+        b_dev = logit_bias.detach().to(f32).reshape(1).contiguous()
+        tb = ops.to_bf16(txt)
+        ib = ops.to_bf16(img)
+        if world_size > 1:
+            t_all, t_ev = _all_gather_bf16(tb, world_size, group)         # the image embeddings never travel
+            if img.is_cuda:
+                _wait_gathers((t_ev,))
+            label0 = B * rank
+        else:
+            t_all, label0 = tb, 0
+        N = t_all.shape[0]
+        t_all8 = _pad_rows8(t_all)
+        need_grad = any(ctx.needs_input_grad[:4])
+        gs = 1.0 / B
+        # fused similarity GEMM + sigmoid loss + its gradient in ONE pass: the [B, N] fp32 logits never reach HBM
+        lr, dl, dsr, dbr = ops.simsig(ib, t_all8, N, label0, gs, s_dev, b_dev, want_grad=need_grad)
+        loss = ops.sum_scale(lr, gs)
+        if need_grad:
+            ctx.save_for_backward(dl, dsr, dbr, ib, t_all8)
+            ctx.meta = (N, world_size, group, img.dtype, txt.dtype, logit_scale.dtype, logit_scale.shape, logit_bias.dtype,
+                        logit_bias.shape)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        dl, dsr, dbr, i_rows, t_all8 = ctx.saved_tensors
+        N, W, group, idt, tdt, sdt, sshape, bdt, bshape = ctx.meta
+        # dl = d loss / d raw (the scale is already folded in), raw = I_rows T_all^T
+        d_i = ops.gemm_nt(dl, ops.transpose_bf16(t_all8), out_f32=True)               # [B, E]
+        d_t_all = ops.gemm_tn(dl, i_rows, f32)[:N]                                    # [W*B, E]
+        # the gather is always differentiable (upstream's neighbour_exchange_with_grad): its backward is a reduce-scatter
+        d_t = _reduce_scatter_fused(d_t_all, W, group) if W > 1 else d_t_all
+        d_s = ops.sum_scale(dsr, 1.0)
+        d_b = ops.sum_scale(dbr, 1.0)
+        g = dloss.to(f32)
+        return ((d_i * g).to(idt), (d_t * g).to(tdt), (d_s * g).to(sdt).reshape(sshape), (d_b * g).to(bdt).reshape(bshape),
+                None, None, None)
+
+
+class SigLipLoss(nn.Module):
+    """Pairwise sigmoid loss of SigLIP (Zhai et al. 2023; element maths: clipa_jax/losses/common.py:25-32) with upstream
+    open_clip's `SigLipLoss` contract: `loss(image_features, text_features, logit_scale, logit_bias, output_dict=False)`
+    -> loss or {"contrastive_loss": loss}.  Per-rank value, exactly upstream's: the sum over this rank's B images and ALL W*B
+    texts of -logsigmoid(y (s I . T^T + b)), divided by B, positives at column B * rank + i.
+
+    MI355X mapping.  No row-wise log-sum-exp: loss terms and gradient come out of ONE pass over the similarity GEMM
+    (`ops.simsig`, csrc/simsig.hip), followed by two gradient GEMMs.  Multi-rank: one bf16 all-gather of the text embeddings
+    (side stream) and one reduce-scatter of their fp32 gradient; the image embeddings never travel.  `bidir` is accepted and
+    has NO effect here: upstream uses it only to choose between a two-way and a one-way neighbour ring for the same set of
+    (image, text) pairs; the all-gather form computes that same sum, so the value and the gradients do not depend on it.
+    Nothing is gathered early, so `ClipLoss.bind` has no counterpart."""
+
+    def __init__(self, cache_labels=False, rank=0, world_size=1, bidir=True, use_horovod=False, group=None):
+        super().__init__()
+        if use_horovod:
+            raise NotImplementedError("clipa_amd: horovod is outside the MI355X path (RCCL via torch.distributed)")
+        self.cache_labels = cache_labels     # labels are implicit (the diagonal at B * rank) in the kernel
+        self.rank = rank
+        self.world_size = world_size
+        self.bidir = bidir
+        self.use_horovod = use_horovod
+        self.group = group
+
+    def forward(self, image_features, text_features, logit_scale, logit_bias, output_dict=False):
+        dev = image_features.device
+        # the reference trainer calls the loss inside torch.autocast (train.py:203-213); the kernels take fixed dtypes
+        with torch.autocast(device_type=dev.type, enabled=False):
+            if not torch.is_tensor(logit_scale):
+                logit_scale = torch.tensor(float(logit_scale), device=dev)
+            if not torch.is_tensor(logit_bias):
+                logit_bias = torch.tensor(float(logit_bias), device=dev)
+            loss = SigLipLossFn.apply(image_features.float(), text_features.float(), logit_scale, logit_bias, self.rank,
+                                      self.world_size, self.group)
+        return {"contrastive_loss": loss} if output_dict else loss

@@ -349,7 +349,8 @@ class VisionTransformer(nn.Module):
 class CLIP(nn.Module):
     """open_clip/model.py:200-274."""
 
-    def __init__(self, embed_dim, vision_cfg, text_cfg, quick_gelu=False, cast_dtype=None, output_dict=False):
+    def __init__(self, embed_dim, vision_cfg, text_cfg, quick_gelu=False, init_logit_scale=np.log(1 / 0.07),
+                 init_logit_bias=None, cast_dtype=None, output_dict=False):
         super().__init__()
         self.output_dict = output_dict
         if isinstance(vision_cfg, dict):
@@ -394,7 +395,10 @@ class CLIP(nn.Module):
             self.register_buffer('attn_mask', mask, persistent=False)   # kept for state/attr parity; the
         else:                                                           # kernel applies the mask itself
             self.attn_mask = None
-        self.logit_scale = nn.Parameter(torch.ones([]) * np.log(1 / 0.07))
+        self.logit_scale = nn.Parameter(torch.ones([]) * init_logit_scale)
+        # SigLIP (upstream open_clip's CLIP): a learnable bias on the logits, consumed by SigLipLoss.  Without it the state_dict
+        # and forward's outputs are exactly the plain-CLIP ones.
+        self.logit_bias = nn.Parameter(torch.ones([]) * init_logit_bias) if init_logit_bias is not None else None
         self._init_text_parameters()
         # operand copies (bf16 / transposed / fp8) are cached per parameter version: drop them whenever weights are loaded
         self.register_load_state_dict_post_hook(lambda module, incompatible_keys: module._cache.clear())
@@ -511,13 +515,18 @@ the host (B integers).  `text_lengths` ([B] integers as a list / tuple / numpy a
             text_features = self.encode_text(text, normalize=True, _varlen=vl)
             logit_scale = self.logit_scale.exp()
         if self.output_dict:
-            return {"image_features": image_features, "text_features": text_features, "logit_scale": logit_scale}
+            out = {"image_features": image_features, "text_features": text_features, "logit_scale": logit_scale}
+            if self.logit_bias is not None:
+                out["logit_bias"] = self.logit_bias
+            return out
+        if self.logit_bias is not None:
+            return image_features, text_features, logit_scale, self.logit_bias
         return image_features, text_features, logit_scale
 
 
 def convert_weights_to_lp(model: nn.Module, dtype=torch.bfloat16):
     """open_clip/model.py:329-351: Linear/Conv/MHA weights+biases, proj, text_projection -> low precision;
-    LayerNorm affine, embeddings, class/positional embeddings, logit_scale stay fp32."""
+    LayerNorm affine, embeddings, class/positional embeddings, logit_scale and logit_bias stay fp32."""
 
     def _convert(l):
         if isinstance(l, (nn.Conv1d, nn.Conv2d, nn.Linear)):

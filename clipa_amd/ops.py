@@ -953,6 +953,36 @@ def simce(rows, cols, n_valid, label0, gscale, scale=None, want_grad=True):
     return loss_rows, dl, dscale_rows
 
 
+def simsig(rows, cols, n_valid, label0, gscale, scale, bias, want_grad=True):
+    """Fused similarity + pairwise sigmoid loss (SigLIP): l = s * rows @ cols[:n_valid]^T + b, y = +1 at column label0 + row
+    and -1 elsewhere; s = scale[0], b = bias[0], f32 DEVICE scalars.  rows [R,E], cols [>= n_valid, E] bf16.  One pass over the
+    GEMM returns loss_rows f32 [R] = sum_n softplus(-y l) (not scaled by gscale) and, with gg = gscale * d loss / d l, the bf16
+    d loss / d (rows @ cols^T) = gg * s [R, n8] (n8 = n_valid rounded up to 8, pad columns zero) | None, the per-row
+    d loss / d s | None and d loss / d b | None.  The fp32 logits never exist in HBM."""
+    _chk(rows, bf16, "rows", 2)
+    _chk(cols, bf16, "cols", 2)
+    _chk(scale, f32, "scale")
+    _chk(bias, f32, "bias")
+    rows, lda = _rowmajor(rows)
+    cols, ldb = _rowmajor(cols)
+    R, E = rows.shape
+    if cols.shape[1] != E or cols.shape[0] < n_valid:
+        raise RuntimeError(f"simsig: cols {tuple(cols.shape)} does not cover {n_valid} x {E}")
+    if scale.numel() != 1 or bias.numel() != 1:
+        raise RuntimeError(f"simsig: scale and bias are scalars, got {tuple(scale.shape)} and {tuple(bias.shape)}")
+    n8 = (n_valid + 7) // 8 * 8
+    dev = rows.device
+    ws, wsb = _workspace("clipa_simsig_workspace", R, n_valid, device=dev)
+    loss_rows = torch.empty(R, device=dev, dtype=f32)
+    dl = torch.empty((R, n8), device=dev, dtype=bf16) if want_grad else None
+    dscale_rows = torch.empty(R, device=dev, dtype=f32) if want_grad else None
+    dbias_rows = torch.empty(R, device=dev, dtype=f32) if want_grad else None
+    with _Timed("simsig", 2.0 * R * n_valid * E):
+        lib.call("clipa_simsig", _p(rows), _p(cols), R, n_valid, E, lda, ldb, _p(scale), _p(bias), label0, float(gscale),
+                 _p(loss_rows), _p(dl), n8, _p(dscale_rows), _p(dbias_rows), _p(ws), wsb, _stream())
+    return loss_rows, dl, dscale_rows, dbias_rows
+
+
 def _distill_operands(rows_s, cols_s, rows_t, cols_t, n_valid, scale_s, scale_t, extra=()):
     for t, name in ((rows_s, "rows_s"), (cols_s, "cols_s"), (rows_t, "rows_t"), (cols_t, "cols_t")):
         _chk(t, bf16, name, 2)

@@ -297,6 +297,18 @@ int clipa_simce_distill_bwd(const void* rows_s, const void* cols_s, const void* 
                             const float* scale_s, const float* scale_t, int64_t label0, float gscale, const float* g_c,
                             const float* g_d, const float* lse_s, const float* lse_t, void* dlogits_bf16, int64_t ldd,
                             float* dscale_rows, void* workspace, int64_t workspace_bytes, void* stream);
+/* Fused similarity + pairwise sigmoid loss of SigLIP (the element maths of clipa_jax/losses/common.py:25-32, sigmoid_xent):
+ * l = s * rows . cols^T + b (rows [R,E], cols [N,E] bf16; s and b read from DEVICE memory, both required), y = +1 at column
+ * label0 + r and -1 elsewhere, t = y * l.  ONE pass over the GEMM: loss_rows[R] = sum_n softplus(-t) (not scaled by gscale),
+ * and - unless the three gradient pointers are all NULL (forward only) - with gg = gscale * (-y) * sigmoid(-t): the bf16
+ * d loss / d (rows.cols^T) = gg * s ([R, ldd], N rounded up to 8 <= ldd <= N rounded up to 256, columns [N, ldd) zero),
+ * dscale_rows[R] = sum_n gg * (rows.cols^T) and dbias_rows[R] = sum_n gg.  The [R,N] logits are never written.
+ * Workspace: clipa_simsig_workspace(R, N) bytes. */
+int64_t clipa_simsig_workspace(int64_t R, int64_t N);
+int clipa_simsig(const void* rows, const void* cols, int64_t R, int64_t N, int64_t E, int64_t lda, int64_t ldb,
+                 const float* scale, const float* bias, int64_t label0, float gscale, float* loss_rows,
+                 void* dlogits_bf16, int64_t ldd, float* dscale_rows, float* dbias_rows, void* workspace,
+                 int64_t workspace_bytes, void* stream);
 int clipa_sum_scale(const float* in, float* out, int64_t n, float scale, int accumulate, void* stream);
 /* Retrieval ranks of the validation metrics (get_clip_metrics, clipa_torch/training/train.py:432-449) without the [N, N]
  * logit matrix.  A (image features) and B (text features) are fp32 [N, E] with leading dimensions lda, ldb (>= E, multiples
