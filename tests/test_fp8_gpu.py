@@ -11,6 +11,8 @@ import pytest
 import torch
 
 from oracle import clip_oracle as O
+from . import tile_walk as TW
+from .test_kernels_gpu import act_grad, check_dev, num_cu, ref_act, rows_by_tile      # shared with the bf16 multi-tile tests
 
 pytestmark = pytest.mark.gpu
 bf16, f32 = torch.bfloat16, torch.float32
@@ -139,7 +141,8 @@ def _debug_set(variant, abl):
 @pytest.mark.parametrize("M,N,K", [(512, 256, 768), (1024, 768, 512), (768, 512, 1280)])
 def test_gemm_f8a_matches_gemm_nt_f8(M, N, K, fmt_a):
     """Whole-tile shapes run on gemm_f8a (four waves, generated main loop, gemm_f8a.hip); every epilogue against the oracle and BIT
-    FOR BIT against gemm_nt_f8_kernel (lib.debug_set(1, .) keeps that kernel), several tiles per workgroup, both A formats."""
+    FOR BIT against gemm_nt_f8_kernel (lib.debug_set(1, .) keeps that kernel), both A formats.  2-12 tiles: one tile per workgroup
+    on a 256-CU part; workgroups that run a second and a third tile are test_gemm_f8a_past_one_tile_per_workgroup's subject."""
     o = ops()
     qa, sa, qb, sb, lin = _f8_operands(M, N, K, fmt_a, 0, seed=31 + fmt_a)
     bias, aux = rnd(N, seed=8, dtype=f32), rnd(M, N, seed=9)
@@ -165,6 +168,199 @@ def test_gemm_f8a_matches_gemm_nt_f8(M, N, K, fmt_a):
     for name, a, b, c in zip(("bias", "gelu", "pre", "quick_gelu", "residual", "gelu_bwd"), old, new, again):
         assert torch.equal(a, b), f"{name}: gemm_f8a differs from gemm_nt_f8_kernel"
         assert torch.equal(b, c), f"{name}: second launch differs"
+
+
+# ---- the persistent fp8 NT GEMMs past one tile per workgroup ----------------------------------------------------------------
+# The fp8 twin of test_kernels_gpu.py::test_gemm_nta_past_one_tile_per_workgroup: see the comment there and tests/tile_walk.py.
+# Between two tiles gemm_f8a also reloads the tile's row scales, bias, column scales and output scales into its LDS window.
+def _f8_tile_operands(M, N, K, fmt_a, seed):
+    """_f8_operands with magnitudes that depend on the tile (tile_walk.tile_factors): the rows of a - and so their scales sa and
+    every row-wise output scale derived from them - by M panel, the rows of b, sb and the bias by N tile.  Sized for matrices of
+    17 000 rows and K up to 4096: row magnitudes exp(N(0, 1/4)) (e^-2 .. e^2 over that many rows) and weights of 0.05 sqrt(512 / K)
+    keep every pre-activation below 60 in magnitude.  The polynomial erf-GELU has a documented tail error of 1.2e-5 |x| beyond
+    |x| = 4.5 (csrc/common.h), which reaches the 2e-3 absolute tolerance of the activation checks at |x| = 166; _f8_operands' own
+    exp(N(0, 1)) rows at K = 4096 put pre-activations of -170 among 17 million.
+    -> bytes and scales of both operands, bias, the bf16 operands themselves (for the row-bound recipes)."""
+    g = torch.Generator().manual_seed(seed)
+    fa, fb = rows_by_tile(M, 7, 13), rows_by_tile(N, 5, 11)
+    a = (torch.randn(M, K, generator=g) * torch.exp(torch.randn(M, 1, generator=g) * 0.5) * fa[:, None]).to(bf16)
+    b = (torch.randn(N, K, generator=g) * (0.05 * math.sqrt(512.0 / K)) * fb[:, None]).to(bf16)
+    bias = torch.randn(N, generator=g) * fb * 0.5
+    qa, sa = cpu_quantize(a, fmt_a)
+    qb, sb = cpu_quantize(b, 0)
+    return qa, sa, qb, sb, bias, a, b
+
+
+def _f8_product(qa, sa, qb, sb, rows=None):
+    if rows is not None:
+        qa, sa = qa[rows], sa[rows]
+    return (qa.double() * sa.double()[:, None]) @ (qb.double() * sb.double()[:, None]).T
+
+
+@pytest.mark.parametrize("name,fmt_a", [("S1", 0), ("S1", 1), ("S2", 0), ("S3", 0)])
+def test_gemm_f8a_past_one_tile_per_workgroup(name, fmt_a):
+    """gemm_f8a with two and three tiles per workgroup (tile_walk.SHAPES; the test FAILS where no workgroup gets a second tile).
+    S1, both A formats: the 12 instantiations of its launcher - NONE, ACT without / with the bf16 / e4m3 pre-activation copy (the
+    three activations), ADD, DACT from bf16 / e4m3 aux, the three producer-quantised activation forms, the producer-quantised DACT
+    from e4m3 bytes with column sums, the emitting DACT (three activations).  S2, S3 (e4m3): plain, ACT with either copy, ADD, the
+    emitting DACT, the quantised DACT with its per-tile column-sum partials.
+      * dispatch: last_gemm and the exact gemm_counts of gemm_f8a and of its e4m3 / quantised / emitting forms, none on gemm_nt_f8_kernel;
+      * the forms gemm_nt_f8_kernel has: bit for bit that kernel (lib.debug_set(1, 0)), itself multi-tile here;
+      * the e4m3, quantised and emitting forms: bit for bit the launches they replace (cast_e4m3 / e4m3_to_bf16 / scale_quantize_rows
+        around that kernel's outputs) - tanh-GELU emit: fewer than 1e-3 of the elements one bf16 step (2^-7) apart, as
+        test_gemm_nt_f8_emit_matches_the_two_launches; column sums at rtol 2e-4 as test_gemm_f8a_producer_quantised_outputs;
+      * bit for bit itself on a second launch and after launches of another shape in between;
+      * plain, pre-activation and activation outputs against the fp64 product of the same de-quantised bytes at 2^-7 / 2e-3, every
+        element (S3: the panels of test_gemm_nta_past_one_tile_per_workgroup)."""
+    o = ops()
+    from clipa_amd import lib
+    M, N, K = TW.SHAPES[name]
+    full = name == "S1"
+    w = TW.walk(M, N, K, 1, num_cu())
+    TW.require_second_tiles(w, f"gemm_f8a {name} on {num_cu()} CUs")
+    qa, sa, qb, sb, bias, a16, b16 = _f8_tile_operands(M, N, K, fmt_a, seed=M + N + fmt_a)
+    A, SA, B, SB, BIAS = qa.view(torch.uint8).to(DEV), sa.to(DEV), qb.view(torch.uint8).to(DEV), sb.to(DEV), bias.to(DEV)
+    gd = torch.Generator(device=DEV).manual_seed(K)
+    AUX = torch.randn(M, N, generator=gd, device=DEV, dtype=f32).to(bf16)
+    one = torch.ones(1, device=DEV)
+    # the recipes of test_gemm_f8a_producer_quantised_outputs / test_gemm_nt_f8_emit_matches_the_two_launches
+    rn, wn = a16.float().norm(dim=1).to(DEV), o.rownorm_max(b16.to(DEV))
+    _, inv = o.row_bound(rn, wn, o.absmax(BIAS), 1.13)
+    _, sodh = o.row_bound(rn, wn, None, 1.13 * 1.13)
+    sg = (torch.rand(M, generator=gd, device=DEV) * 0.02 + 1e-3)
+    t = o.rowscale_max(SA, sg)
+    kw = dict(fmt_a=fmt_a, alpha=0.75)
+    acts = (0, 1, 2)
+    # the e4m3 operand of the GELU-backward forms: this product's own pre-activation bytes (always written by gemm_f8a)
+    _, H8 = o.gemm_nt_f8(A, SA, B, SB, BIAS, epi=o.EPI_ACT, act=0, want_pre="e4m3", **kw)
+    HB = o.e4m3_to_bf16(H8)
+
+    def both(r):           # the forms gemm_nt_f8_kernel has too
+        r["bias"] = o.gemm_nt_f8(A, SA, B, SB, BIAS, **kw)
+        r["act_pre"], r["pre"] = o.gemm_nt_f8(A, SA, B, SB, BIAS, epi=o.EPI_ACT, act=0, want_pre=True, **kw)
+        r["residual"] = o.gemm_nt_f8(A, SA, B, SB, None, epi=o.EPI_ADD, aux=AUX, **kw)
+        if full:
+            for act in acts:
+                r[f"act{act}"] = o.gemm_nt_f8(A, SA, B, SB, BIAS, epi=o.EPI_ACT, act=act, **kw)
+            r["gelu_bwd"] = o.gemm_nt_f8(A, None, B, SB, BIAS, epi=o.EPI_DACT, act=0, aux=AUX, **kw)
+        return r
+
+    def composed(r):       # the launches the other forms replace, around gemm_nt_f8_kernel
+        r["act_pre8"], r["pre8"] = r["act_pre"], o.cast_e4m3(r["pre"])
+        dh = o.gemm_nt_f8(A, SA, B, SB, None, epi=o.EPI_DACT, act=0, aux=HB, **kw)
+        r["q_gelu_bwd8"], r["colsum"] = o.scale_quantize_rows(dh, sodh, one), dh.double().sum(0)
+        r["colsum_atol"] = 1e-6 * float(dh.float().abs().sum(0).max())
+        for act in acts:
+            r[f"emit_dh{act}"] = o.gemm_nt_f8(A, SA, B, SB, None, epi=o.EPI_DACT, act=act, aux=HB, fmt_a=fmt_a)
+            r[f"emit_x8_{act}"] = o.scale_quantize_rows(H8, SA, t, act=act)
+        if full:
+            r["gelu_bwd8"] = dh
+            r["q_act"] = r["q_act_pre"] = r["q_act_pre8"] = o.scale_quantize_rows(r["act0"], inv, one)
+            r["q_pre"], r["q_pre8"] = r["pre"], r["pre8"]
+        return r
+
+    def fused(r):
+        r["act_pre8"], r["pre8"] = o.gemm_nt_f8(A, SA, B, SB, BIAS, epi=o.EPI_ACT, act=0, want_pre="e4m3", **kw)
+        r["q_gelu_bwd8"], r["colsum"] = o.gemm_nt_f8(A, SA, B, SB, None, epi=o.EPI_DACT, act=0, aux=H8, out_scale=sodh, want_colsum=True, **kw)
+        for act in acts:
+            r[f"emit_dh{act}"], r[f"emit_x8_{act}"] = o.gemm_nt_f8_emit(A, SA, B, SB, H8, t, act=act, fmt_a=fmt_a)
+        if full:
+            r["gelu_bwd8"] = o.gemm_nt_f8(A, SA, B, SB, None, epi=o.EPI_DACT, act=0, aux=H8, **kw)
+            r["q_act"] = o.gemm_nt_f8(A, SA, B, SB, BIAS, epi=o.EPI_ACT, act=0, out_scale=inv, **kw)
+            r["q_act_pre"], r["q_pre"] = o.gemm_nt_f8(A, SA, B, SB, BIAS, epi=o.EPI_ACT, act=0, want_pre=True, out_scale=inv, **kw)
+            r["q_act_pre8"], r["q_pre8"] = o.gemm_nt_f8(A, SA, B, SB, BIAS, epi=o.EPI_ACT, act=0, want_pre="e4m3", out_scale=inv, **kw)
+        return r
+
+    loose = ("colsum", "colsum_atol", "emit_dh1")
+
+    def same(what, x, y, skip=()):
+        assert set(x) - {"colsum_atol"} == set(y) - {"colsum_atol"}
+        for k in y:
+            if k not in skip and k != "colsum_atol":
+                assert x[k].dtype == y[k].dtype and torch.equal(x[k], y[k]), f"{name} {k}: {what}"
+
+    other = TW.SHAPES["S2" if name == "S1" else "S1"]
+    qa2, sa2, qb2, sb2, bias2, _, _ = _f8_tile_operands(*other, 0, seed=5)
+    A2, SA2, B2, SB2, BIAS2 = qa2.view(torch.uint8).to(DEV), sa2.to(DEV), qb2.view(torch.uint8).to(DEV), sb2.to(DEV), bias2.to(DEV)
+    try:
+        h = _debug_set(1, 0)
+        lib.gemm_counts(reset=True)
+        old = composed(both({}))
+        c = lib.gemm_counts()
+        assert h.last_gemm() == 7 and c[6] == 0, c
+        _debug_set(0, 0)
+        lib.gemm_counts(reset=True)
+        new = fused(both({}))
+        c = lib.gemm_counts()
+        # gemm_f8a launches: [6] all, [12] with the e4m3 copy, [13] DACT from e4m3 bytes (the emitting ones included), [14] with a
+        # quantised output, [0] emitting; [7] gemm_nt_f8_kernel
+        want = (16, 1, 4, 4, 3, 0) if full else (8, 1, 3, 1, 3, 0)
+        assert h.last_gemm() == 6 and (c[6], c[12], c[13], c[14], c[0], c[7]) == want, f"{name}: dispatch {c}"
+        same("gemm_f8a differs from the launches around gemm_nt_f8_kernel", old, new, skip=loose)
+        torch.testing.assert_close(new["colsum"].double(), old["colsum"], rtol=2e-4, atol=old["colsum_atol"])
+        bad = new["emit_dh1"] != old["emit_dh1"]      # tanh-GELU: the table's act'(x) and the polynomial epilogue's differ in the last bit for a few codes
+        assert float(bad.float().mean()) < 1e-3
+        if bool(bad.any()):
+            x, y = new["emit_dh1"].float(), old["emit_dh1"].float()
+            assert float(((x - y).abs() / y.abs().clamp_min(1e-30))[bad].max()) <= 2 ** -7
+        assert torch.equal(new["pre8"], H8)
+        same("second launch differs", new, fused(both({})))
+        # another shape in between: other tile counts, other descriptors, other vectors left in the LDS window
+        o.gemm_nt_f8(A2, SA2, B2, SB2, BIAS2, epi=o.EPI_ACT, act=1, want_pre="e4m3")
+        o.gemm_nt_f8(A2, None, B2, None)
+        assert h.last_gemm() == 6
+        same("differs after a launch of another shape", new, fused(both({})))
+    finally:
+        _debug_set(0, 0)
+    del old, A2, B2
+
+    if name == "S3":
+        panels = TW.panels_to_check(w)
+        assert len(panels) >= 8
+        rows = torch.cat([torch.arange(256 * p, 256 * p + 256) for p in panels])
+    else:
+        rows = torch.arange(M)
+    lin = (_f8_product(qa, sa, qb, sb, rows) * 0.75 + bias.double()).to(DEV)
+    rows = rows.to(DEV)
+    check_dev("bias", new["bias"][rows], lin, 2 ** -7, 2e-3)
+    check_dev("pre", new["pre"][rows], lin, 2 ** -7, 2e-3)
+    pre = new["pre"][rows].double()
+    for act in (acts if full else ()):
+        check_dev(f"act {act}", new[f"act{act}"][rows], ref_act(pre, act), 2 ** -7, 2e-3)
+    check_dev("act (with the e4m3 copy)", new["act_pre8"][rows], ref_act(pre, 0), 2 ** -7, 2e-3)
+
+
+def test_gemm_nt_f8_ragged_shape_past_one_tile_per_workgroup():
+    """gemm_nt_f8_kernel, ragged in M, N and K, with 603 tiles: two and three per workgroup.  The epilogues and tolerances of
+    test_gemm_nt_f8_epilogues, every element against the fp64 product of the same bytes, tile-dependent scales."""
+    o = ops()
+    from clipa_amd import lib
+    M, N, K = TW.RAGGED_F8
+    w = TW.walk(M, N, K, 1, num_cu())
+    TW.require_second_tiles(w, f"gemm_nt_f8_kernel {(M, N, K)} on {num_cu()} CUs")
+    qa, sa, qb, sb, bias, _, _ = _f8_tile_operands(M, N, K, 0, seed=21)
+    A, SA, B, SB, BIAS = qa.view(torch.uint8).to(DEV), sa.to(DEV), qb.view(torch.uint8).to(DEV), sb.to(DEV), bias.to(DEV)
+    AUX = torch.randn(M, N, generator=torch.Generator(device=DEV).manual_seed(9), device=DEV, dtype=f32).to(bf16)
+    v = (_f8_product(qa, sa, qb, sb) + bias.double()).to(DEV).to(bf16).double()
+    aux = AUX.double()
+    for act in (0, 1, 2):
+        prev = None
+        for rep in range(2):                           # the second launch re-uses ring state
+            out, pre = o.gemm_nt_f8(A, SA, B, SB, BIAS, epi=o.EPI_ACT, act=act, want_pre=True)
+            assert lib.last_gemm() == 7
+            one = o.gemm_nt_f8(A, SA, B, SB, BIAS, epi=o.EPI_ACT, act=act)
+            add = o.gemm_nt_f8(A, SA, B, SB, BIAS, epi=o.EPI_ADD, aux=AUX)
+            dact = o.gemm_nt_f8(A, SA, B, SB, BIAS, epi=o.EPI_DACT, act=act, aux=AUX)
+            assert torch.equal(out, one), "activation epilogue with / without the pre-activation copy"
+            got = (out, pre, add, dact)
+            if prev is not None:
+                assert all(torch.equal(x, y) for x, y in zip(prev, got)), "second launch differs"
+            prev = got
+        check_dev("pre-activation", pre, v, 2 ** -7, 2e-3)
+        check_dev("act", out, ref_act(pre.double(), act), 2 ** -7, 2e-3)
+        if act == 0:
+            check_dev("residual add", add, v + aux, 2 ** -6, 2e-2)
+        check_dev("act backward", dact, v * act_grad(aux, act), 2 ** -6, 6e-3)
 
 
 def test_gemm_nt_f8_production_rows():
@@ -227,9 +423,11 @@ def test_layernorm_fwd_q8(D, rows):
 #                                                      cosine >= 0.95, norm within 22 %
 #   BASELINE dimensions (12-32 blocks, batch 2-4):     features |err| <= 5e-2, loss <= 3 %, per-tensor gradient cosine >= 0.85
 #                                                      (median >= 0.92), norm within 25 %
-# e4m3 rounding is ~3 % rms per operand element and unbiased; it averages out over the tokens of a batch, so the
-# per-tensor cosine at batch 2-4 is the worst case, not what a 4096-pair batch sees.  The same recipe run through the
-# torch-CPU stand-in ops (tests/test_engine_cpu.py::test_fp8_orchestration) gives 0.92-0.95 at these batch sizes.
+# e4m3 rounding is ~3 % rms per operand element and unbiased.  That it "averages out over the tokens of a batch" in the per-tensor
+# cosines was this comment's claim until it was measured (test_fp8_production_kernels_end_to_end: the same 2-layer model holds a
+# median of ~0.990 at 8 and at 128 pairs, the larger batch 0.002 lower): what a 4096-pair batch sees at 12-32 blocks is not
+# measured.  The same recipe run through the torch-CPU stand-in ops (tests/test_engine_cpu.py::test_fp8_orchestration) gives
+# 0.92-0.95 at batch 2-4.
 import clipa_amd  # noqa: E402
 from .conftest import load_golden  # noqa: E402
 
@@ -733,3 +931,159 @@ def test_gemm_nt_f8_emit_matches_the_two_launches(M, N, K, fmt):
     z = torch.zeros(1, device=DEV)
     _, xz = o.gemm_nt_f8_emit(dq, ds, wq, ws, h8, z, act=0, fmt_a=fmt)
     assert torch.equal(xz, o.scale_quantize_rows(h8, ds, z, act=0))
+
+
+# ---- fp8 through the model with the production kernels dispatched -----------------------------------------------------------
+def _fp8_parity_figures(m, out, loss, sd, cfg, images, texts):
+    """Features, loss and every parameter gradient of one fp8 step against the fp32 oracle on the same weights and batch.
+    -> dict of figures; the vectors that are plain sums over the batch of the pooled rows' gradients (the split of
+    test_model_gpu.py::test_production_kernels_end_to_end) are reported apart from the other tensors."""
+    osd = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    fi, ft, s = O.clip_forward(osd, O.oracle_cfg(cfg), O.normalize_images(images), texts)
+    lf, _ = O.clip_loss(fi, ft, s)
+    lf.backward()
+    i, t = out["image_features"].float().cpu(), out["text_features"].float().cpu()
+    ref = {k: v.grad for k, v in osd.items() if v.grad is not None}
+    got = {k: p.grad for k, p in m.named_parameters() if p.grad is not None}
+    assert sorted(got) == sorted(ref)
+    nv, nt = cfg["vision_cfg"]["layers"] - 1, cfg["text_cfg"]["layers"] - 1
+    pooled_sum = ("ln_final.", "visual.ln_post.", f"transformer.resblocks.{nt}.mlp.c_proj.bias", f"transformer.resblocks.{nt}.attn.out_proj.bias",
+                  f"visual.transformer.resblocks.{nv}.mlp.c_proj.bias", f"visual.transformer.resblocks.{nv}.attn.out_proj.bias")
+    rows = {False: [], True: []}
+    for n in sorted(ref):
+        a, b = got[n].double().cpu().reshape(-1), ref[n].double().reshape(-1)
+        assert torch.isfinite(a).all(), n
+        if a.numel() == 1 or float(b.norm()) < 1e-7:
+            continue
+        rows[n.startswith(pooled_sum)].append((float(torch.dot(a, b) / (a.norm() * b.norm())), float(a.norm() / b.norm()), n))
+    main, pooled = sorted(rows[False]), sorted(rows[True])
+    mats = sorted(c for c, _, n in main if "resblocks" in n and n.endswith("weight") and got[n].dim() == 2)
+    return {"feature": max(float((i - fi.detach()).abs().max()), float((t - ft.detach()).abs().max())),
+            "loss": abs(float(loss) - float(lf)) / float(lf),
+            "cos_min": main[0][0], "cos_min_name": main[0][2], "cos_median": main[len(main) // 2][0],
+            "norm_lo": min(r for _, r, _ in main), "norm_hi": max(r for _, r, _ in main),
+            "pooled_cos_min": pooled[0][0], "pooled_cos_min_name": pooled[0][2],
+            "pooled_norm_lo": min(r for _, r, _ in pooled), "pooled_norm_hi": max(r for _, r, _ in pooled),
+            "block_matrix_cos_median": mats[len(mats) // 2], "block_matrices": len(mats)}
+
+
+def _fmt_figures(tag, f):
+    return (f"[{tag}] feature err {f['feature']:.4f}, loss rel {f['loss']:.5f}, gradient cosine min {f['cos_min']:.4f} ({f['cos_min_name']}) "
+            f"median {f['cos_median']:.4f}, norm ratio {f['norm_lo']:.3f}..{f['norm_hi']:.3f}; pooled-sum vectors: cosine min "
+            f"{f['pooled_cos_min']:.4f} ({f['pooled_cos_min_name']}), norm ratio {f['pooled_norm_lo']:.3f}..{f['pooled_norm_hi']:.3f}; "
+            f"median cosine of the {f['block_matrices']} block weight matrices {f['block_matrix_cos_median']:.4f}")
+
+
+# name -> image size and what an MI355X measures at batch 128 (profiles/r07_pytest_fp8_production_end_to_end.log): feature error,
+# relative loss error, minimum / median gradient cosine and largest norm deviation of the tensors that are not pooled sums, the
+# same two of the pooled-sum vectors, median cosine of the 16 block weight matrices, and how far that median lies BELOW the one
+# of the first 8 samples.  Every asserted bound is 1.5 x the measured distance from perfect (_cos_bound / _dev_bound), all of
+# them inside the floors the full-dimension fixtures are held to (test_fp8_full_dims_match_reference_golden: 0.89 / 0.94 / 22 % /
+# 4e-2 / 2 %).  The engine is bit-reproducible at a fixed seed: the margin is for later legitimate re-orderings of fp32 sums.
+FP8_E2E = {
+    "ViT-L-16": dict(image_size=112, feature=0.0148, loss=0.00005, cos_min=0.9588, cos_median=0.9899, norm=0.053,
+                     pooled_cos_min=0.9904, pooled_norm=0.063, block_matrix_cos_median=0.9897, below_batch_8=0.0019),
+    "ViT-H-14": dict(image_size=98, feature=0.0126, loss=0.00023, cos_min=0.9665, cos_median=0.9912, norm=0.028,
+                     pooled_cos_min=0.9911, pooled_norm=0.028, block_matrix_cos_median=0.9905, below_batch_8=0.0015),
+}
+FP8_FLOORS = dict(feature=4e-2, loss=0.02, cos_min=0.89, cos_median=0.94, norm=0.22)
+
+
+def _cos_bound(measured):
+    return 1.0 - 1.5 * (1.0 - measured)
+
+
+def _dev_bound(measured):
+    return 1.5 * measured
+
+
+@pytest.mark.parametrize("name", list(FP8_E2E))
+def test_fp8_production_kernels_end_to_end(name):
+    """The fp8 twin of test_model_gpu.py::test_production_kernels_end_to_end, at the smallest size that reaches the whole-tile
+    kernels: 2 layers at the named model's widths, 7 x 7 patches + class token = 50 image tokens, 32 text tokens, batch 128 (50 is
+    2 mod 4: B x 50 is a multiple of 256 from B = 128 on) - 6400 image rows, 4096 text rows, every block GEMM on gemm_f8a /
+    gemm_tn8, the in-projection and c_fc products with 375-500 tiles (two tiles per workgroup on 256 CUs).  precision="fp8", keep
+    plan from bench.plan_keep_tensors with bench.KEEP_VALUE_MS_PER_GB_FP8 (everything fits: each block keeps the e4m3 pre-activation),
+    LastBlockFn on both towers.  Features, loss and every gradient against the fp32 oracle on the same weights and batch.
+
+    The same model on the first 8 samples (400 image rows: ragged, gemm_nt_f8_kernel and gemm_tn8's byte-gather kernel; 256 text
+    rows: one M panel of gemm_f8a) tests "e4m3 rounding averages out over the tokens of a batch" (VERDICT weak 1b).  It
+    does NOT, at these sizes: the median cosine of the 16 block weight matrices is 0.9897 / 0.9905 (ViT-L-16 / ViT-H-14) at batch
+    128 against 0.9916 / 0.9920 at batch 8, the minimum (block 0's c_proj.weight of the image tower, both batches) 0.9588 / 0.9665
+    against 0.9719 / 0.9644.  Asserted is what is measured: batch 128 is not more than 1.5 x the measured 0.0019 / 0.0015 below
+    batch 8 (that it is not above is a finding, not a requirement).
+
+    Measured on an MI355X (profiles/r07_pytest_fp8_production_end_to_end.log), batch 128 | batch 8:
+      ViT-L-16  feature error 0.0148 | 0.0134, loss 0.005 % | 0.19 %, cosine min 0.9588 | 0.9719 median 0.9899 | 0.9916, norm ratio
+                0.998..1.053 | 0.990..1.017; pooled-sum vectors cosine min 0.9904 | 0.9913, norm ratio 1.021..1.063 | 0.970..1.005
+      ViT-H-14  feature error 0.0126 | 0.0109, loss 0.023 % | 0.025 %, cosine min 0.9665 | 0.9644 median 0.9912 | 0.9917, norm ratio
+                0.972..1.000 | 0.978..1.036; pooled-sum vectors cosine min 0.9911 | 0.9922, norm ratio 0.972..0.994 | 0.987..1.014"""
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+    from clipa_amd import lib
+    spec = FP8_E2E[name]
+    cfg = clipa_amd.get_model_config(name)
+    cfg["vision_cfg"]["layers"], cfg["text_cfg"]["layers"] = 2, 2
+    cfg["vision_cfg"]["image_size"], cfg["text_cfg"]["context_length"] = spec["image_size"], 32
+    B, Lv, Lt = 128, 50, 32
+    torch.manual_seed(7)
+    m = clipa_amd.CLIP(**cfg, output_dict=True)
+    clipa_amd.convert_weights_to_lp(m, torch.bfloat16)
+    sd = {k: v.detach().float().clone() for k, v in m.state_dict().items()}
+    m.to(DEV)
+    vt, tt = m.visual.transformer, m.transformer
+    vt.fp8 = tt.fp8 = True                              # what create_model(precision="fp8") sets (factory.py)
+    m.set_grad_checkpointing(True)
+    images, texts = O.synthetic_batch(B, spec["image_size"], Lt, cfg["text_cfg"]["vocab_size"], seed=11)
+    tok = {"v": B * Lv, "t": B * Lt}
+    tb = {(tw, n): tr.tensor_keep_bytes(tok[tw], n) for tw, tr in (("v", vt), ("t", tt)) for n in ("h8", "h", "a", "x1", "qkv")}
+    plan = bench.plan_keep_tensors(64 << 30, {"v": 2, "t": 2}, tb, bench.KEEP_VALUE_MS_PER_GB_FP8, ("v", "t"))
+    assert all(plan[tw][n] == 2 for tw in ("v", "t") for n in ("h8", "a", "x1", "qkv")), plan
+    vt.keep_counts, tt.keep_counts = dict(plan["v"]), dict(plan["t"])
+
+    def step(b):
+        lib.gemm_counts(reset=True)
+        m.zero_grad(set_to_none=True)
+        out = m(images[:b].to(DEV), texts[:b].to(DEV))
+        loss = clipa_amd.ClipLoss()(**out, output_dict=True)["contrastive_loss"]
+        loss.backward()
+        torch.cuda.synchronize()
+        c = lib.gemm_counts()
+        print(f"[{name} fp8, batch {b}] launches: gemm_f8a {c[6]} (e4m3 copy {c[12]}, e4m3 operand {c[13]}, quantised output {c[14]}, emitting "
+              f"{c[0]}), gemm_nt_f8_kernel {c[7]}, gemm_tn8 {c[8]}, its byte-gather kernel alone {c[9]}, gemm_nta {c[2]}, gemm_nt2 {c[1]}")
+        return c, _fp8_parity_figures(m, out, loss, sd, cfg, images[:b], texts[:b])
+
+    c, big = step(B)
+    print(_fmt_figures(f"{name} x 2 layers, fp8, batch {B}: production kernels end to end", big))
+    # gemm_f8a, per tower (everything kept, nothing recomputed):
+    #   block 0 forward (engine._block_forward_fp8): in-projection, out-projection, c_fc with the e4m3 copy, c_proj            4
+    #   block 0 backward (_block_backward_fp8): the emitting GELU-backward product of c_proj (reads the kept e4m3 bytes), the
+    #     input gradients of c_fc, of the out-projection and of the in-projection                                              4
+    #   block 1 (LastBlockFn): the in-projection and its input gradient; its B pooled rows take the bf16 GEMMs                  2
+    # two towers: 20 launches, 2 with the e4m3 copy, 2 from e4m3 bytes - both of them emitting -, none with a quantised output
+    # (fp8_predicted_scales is off), nothing left on gemm_nt_f8_kernel.  gemm_tn8: the 4 + 1 block weight gradients of a tower.
+    assert (c[6], c[12], c[13], c[0], c[14]) == (20, 2, 2, 2, 0), c
+    assert c[7] == 0, c
+    assert c[8] >= 10, c
+    c8, small = step(8)
+    print(_fmt_figures(f"{name} x 2 layers, fp8, batch 8: generic kernels", small))
+    # 8 x 50 = 400 image rows are ragged: the image tower's 10 products run on gemm_nt_f8_kernel; 8 x 32 = 256 text rows are one
+    # whole M panel: the text tower's stay on gemm_f8a (one tile per workgroup)
+    assert (c8[6], c8[7], c8[8]) == (10, 10, 0), c8
+    for k in ("feature", "loss", "norm"):
+        assert _dev_bound(spec[k]) <= FP8_FLOORS[k]
+    assert _cos_bound(spec["cos_min"]) >= FP8_FLOORS["cos_min"] and _cos_bound(spec["cos_median"]) >= FP8_FLOORS["cos_median"]
+    assert big["feature"] < _dev_bound(spec["feature"]) and big["loss"] < _dev_bound(spec["loss"]), (big["feature"], big["loss"])
+    assert big["cos_min"] > _cos_bound(spec["cos_min"]), (big["cos_min"], big["cos_min_name"])
+    assert big["cos_median"] > _cos_bound(spec["cos_median"]), big["cos_median"]
+    assert max(1.0 - big["norm_lo"], big["norm_hi"] - 1.0) < _dev_bound(spec["norm"]), (big["norm_lo"], big["norm_hi"])
+    assert big["pooled_cos_min"] > _cos_bound(spec["pooled_cos_min"]), (big["pooled_cos_min"], big["pooled_cos_min_name"])
+    assert max(1.0 - big["pooled_norm_lo"], big["pooled_norm_hi"] - 1.0) < _dev_bound(spec["pooled_norm"]), (big["pooled_norm_lo"], big["pooled_norm_hi"])
+    assert big["block_matrix_cos_median"] > _cos_bound(spec["block_matrix_cos_median"]), big["block_matrix_cos_median"]
+    # the rounding does not average out over the batch (see the docstring): measured 0.0019 / 0.0015 BELOW the batch of 8
+    assert big["block_matrix_cos_median"] >= small["block_matrix_cos_median"] - _dev_bound(spec["below_batch_8"]), \
+        (big["block_matrix_cos_median"], small["block_matrix_cos_median"])

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from oracle import clip_oracle as O
+from . import tile_walk as TW
 
 pytestmark = pytest.mark.gpu
 bf16, f32 = torch.bfloat16, torch.float32
@@ -101,8 +102,9 @@ NTA, NT2, TNA = 2, 1, 5                  # kernel families reported by lib.last_
 
 @pytest.mark.parametrize("M,N,K", [(1024, 768, 512), (2304, 512, 256), (512, 1024, 1152)])
 def test_gemm_nta_small_shapes_every_epilogue_bitwise_vs_nt2(M, N, K):
-    """The four-wave hand-scheduled kernel (gemm_nta.hip) on SMALL whole-tile shapes - several tiles per persistent workgroup
-    when there are fewer workgroups than tiles is exercised by the production-width tests; here 8-18 tiles, 4-18 K steps,
+    """The four-wave hand-scheduled kernel (gemm_nta.hip) on SMALL whole-tile shapes: 8-18 tiles, so ONE tile per persistent
+    workgroup on a 256-CU part - a workgroup that goes on to a second tile is test_gemm_nta_past_one_tile_per_workgroup's
+    subject, not this test's (nor the production-width tests': sampled rows, act 0, a tolerance); here 4-18 K steps,
     every epilogue, against fp64 AND bit for bit against gemm_nt2 (the round-1/2 kernel it replaced), and the dispatch itself:
     a silent regression of whole-tile shapes to gemm_nt2 would otherwise pass every value test."""
     o = ops()
@@ -134,6 +136,204 @@ def test_gemm_nta_small_shapes_every_epilogue_bitwise_vs_nt2(M, N, K):
     for name, x, y, z in zip(names, old, new, again):
         assert torch.equal(x, y), f"{name}: gemm_nta differs from gemm_nt2"
         assert torch.equal(y, z), f"{name}: second launch differs"
+
+
+# ---- the persistent NT GEMMs past one tile per workgroup -------------------------------------------------------------------
+# gemm_nta / gemm_nt2 launch min(tiles, CUs) workgroups and each walks its share of the tile list (tests/tile_walk.py restates
+# the walk).  What can go wrong between two tiles of one workgroup - the next tile's first two K steps fetched by the last two of
+# this one, the zero-length descriptors behind the last tile, the per-tile bias reload, the split over the XCDs, the ragged last
+# group - only runs when there are more tiles than CUs: tile_walk.SHAPES, 260 and 603 tiles.
+def num_cu():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def rows_by_tile(n, stride, period):
+    return torch.tensor(TW.tile_factors(-(-n // 256), stride, period), dtype=f32).repeat_interleave(256)[:n]
+
+
+def tile_scaled_operands(M, N, K, seed):
+    """bf16 operands whose magnitude depends on the tile (tile_walk.tile_factors): rows of a by M panel, rows of b and the bias by
+    N tile.  alpha = 0.5 is folded in: 0.5 a b^T has unit variance times the two factors."""
+    g = torch.Generator().manual_seed(seed)
+    fa, fb = rows_by_tile(M, 7, 13), rows_by_tile(N, 5, 11)
+    a = (torch.randn(M, K, generator=g) * fa[:, None]).to(bf16)
+    b = (torch.randn(N, K, generator=g) * (fb * 2.0 / math.sqrt(K))[:, None]).to(bf16)
+    bias = torch.randn(N, generator=g) * fb * 0.5
+    return a, b, bias
+
+
+def check_dev(name, got, ref, rtol, atol):
+    """check() with the comparison on the device: `ref` is an fp64 tensor there (a CPU fp64 product, uploaded)."""
+    assert got.shape == ref.shape, f"{name}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
+    got = got.double()
+    assert bool(torch.isfinite(got).all()), f"{name}: non-finite output"
+    over = (got - ref).abs() - (atol + rtol * ref.abs())
+    nbad = int((over > 0).sum())
+    if nbad:
+        i = int(torch.argmax(over.reshape(-1)))
+        idx = np.unravel_index(i, tuple(got.shape))
+        raise AssertionError(f"{name}: {nbad}/{got.numel()} outside tol; worst at {idx}: got {got.reshape(-1)[i].item():.6g} "
+                             f"ref {ref.reshape(-1)[i].item():.6g}")
+
+
+def act_grad(x, act):
+    x = x.clone().requires_grad_(True)
+    ref_act(x, act).sum().backward()
+    return x.grad
+
+
+def _e4m3_one_step_apart(got8, want8, min_same):
+    """Two e4m3 roundings of the same value, one of them through bf16 first (the unfused GEMM + cast): equal bytes but for the
+    double-rounding ties (a value within half a bf16 ulp, 2^-9, of an e4m3 midpoint, steps of 2^-3: 2 * 2^-9 / 2^-3 = 3 %), and
+    never more than one e4m3 step apart."""
+    o = ops()
+    same = float((got8 == want8).float().mean())
+    assert same > min_same, same
+    gf, wf = o.e4m3_to_bf16(got8).float(), o.e4m3_to_bf16(want8).float()
+    assert bool(torch.isfinite(gf).all())
+    step = wf.abs().clamp_min(2.0 ** -6) * 2.0 ** -3
+    assert bool(((gf - wf).abs() <= step * 1.001).all())
+
+
+@pytest.mark.parametrize("name", ["S1", "S2", "S3"])
+def test_gemm_nta_past_one_tile_per_workgroup(name):
+    """gemm_nta with two and three tiles per workgroup (tile_walk.SHAPES; the test FAILS on a part with so many CUs that no
+    workgroup gets a second tile), every instantiation its launcher reaches - plain, ACT x {erf, tanh, quick}, ACT with the bf16 /
+    e4m3 pre-activation copy, ADD, DACT from bf16 / e4m3 aux, DACT from e4m3 aux that also writes the activation:
+      * dispatched to gemm_nta (last_gemm, gemm_counts), never silently to gemm_nt2;
+      * bit for bit gemm_nt2 (lib.debug_set(1, 0)), itself multi-tile here; the e4m3 forms against the composition gemm_nt2 offers
+        (cast of the bf16 pre-activation: one double rounding apart; GELU-backward from the decoded bytes; activation_fwd);
+      * bit for bit itself on a second launch and after launches of another shape in between;
+      * against the fp64 product of the same operands, every element (S3: the full rows of the first and last M panel, of every
+        panel holding a tile that is not its workgroup's first, at least eight), at the tolerances of the small-shape and the
+        production-width tests;
+      * S1: every generated schedule the library builds and tile groups of 2, 5 and 16 panels give the same bits."""
+    o = ops()
+    from clipa_amd import lib
+    M, N, K = TW.SHAPES[name]
+    w = TW.walk(M, N, K, 2, num_cu())
+    TW.require_second_tiles(w, f"gemm_nta {name} on {num_cu()} CUs")
+    a, b, bias = tile_scaled_operands(M, N, K, seed=M + N)
+    A, B, BIAS = a.to(DEV), b.to(DEV), bias.to(DEV)
+    AUX = torch.randn(M, N, generator=torch.Generator(device=DEV).manual_seed(K), device=DEV, dtype=f32).to(bf16)
+    # the e4m3 operand of the GELU-backward forms: this product's own pre-activation bytes (tile-dependent magnitudes)
+    _, H8 = o.gemm_nt(A, B, BIAS, alpha=0.5, epi=o.EPI_ACT, act=0, want_pre="e4m3")
+    HB = o.e4m3_to_bf16(H8)
+    kw = dict(alpha=0.5)
+
+    def run(fused=True):
+        r = {"bias": o.gemm_nt(A, B, BIAS, **kw)}
+        for act in (0, 1, 2):
+            r[f"act{act}"] = o.gemm_nt(A, B, BIAS, epi=o.EPI_ACT, act=act, **kw)
+        r["act_pre"], r["pre"] = o.gemm_nt(A, B, BIAS, epi=o.EPI_ACT, act=0, want_pre=True, **kw)
+        r["residual"] = o.gemm_nt(A, B, BIAS, epi=o.EPI_ADD, aux=AUX, **kw)
+        r["gelu_bwd"] = o.gemm_nt(A, B, BIAS, epi=o.EPI_DACT, act=0, aux=AUX, **kw)
+        if fused:
+            r["act_pre8"], r["pre8"] = o.gemm_nt(A, B, BIAS, epi=o.EPI_ACT, act=0, want_pre="e4m3", **kw)
+            r["gelu_bwd8"] = o.gemm_nt(A, B, BIAS, epi=o.EPI_DACT, act=0, aux=H8, **kw)
+            for act in (0, 1, 2):
+                r[f"gelu_bwd8_act{act}"], r[f"act_of_aux{act}"] = o.gemm_nt(A, B, BIAS, epi=o.EPI_DACT, act=act, aux=H8, want_act=True, **kw)
+        else:       # what gemm_nt2 offers for the e4m3 forms (ops._plan_nt's unfused steps)
+            r["act_pre8"], r["pre8"] = r["act_pre"], o.cast_e4m3(r["pre"])
+            r["gelu_bwd8"] = o.gemm_nt(A, B, BIAS, epi=o.EPI_DACT, act=0, aux=HB, **kw)
+            for act in (0, 1, 2):
+                r[f"gelu_bwd8_act{act}"] = o.gemm_nt(A, B, BIAS, epi=o.EPI_DACT, act=act, aux=HB, **kw)
+                r[f"act_of_aux{act}"] = o.activation_fwd(H8, act)
+        return r
+
+    def same(what, x, y, skip=()):
+        assert x.keys() == y.keys()
+        for k in x:
+            if k not in skip:
+                assert x[k].dtype == y[k].dtype and torch.equal(x[k], y[k]), f"{name} {k}: {what}"
+
+    other = TW.SHAPES["S2" if name == "S1" else "S1"]
+    a2, b2, bias2 = (t.to(DEV) for t in tile_scaled_operands(*other, seed=5))
+    try:
+        _debug_set(1, 0)
+        old = run(fused=False)
+        assert _last_gemm() == NT2
+        _debug_set(0, 0)
+        lib.gemm_counts(reset=True)
+        new = run()
+        c = lib.gemm_counts()
+        # 12 launches, all on gemm_nta: 1 with the e4m3 copy, 4 from e4m3 aux of which 3 write the activation
+        assert _last_gemm() == NTA and (c[2], c[10], c[11], c[15]) == (12, 1, 4, 3), f"{name}: not every form ran on gemm_nta: {c}"
+        same("gemm_nta differs from gemm_nt2", old, new, skip=("pre8",))
+        _e4m3_one_step_apart(new["pre8"], old["pre8"], 0.95)
+        assert torch.equal(new["pre8"], H8)
+        assert torch.equal(new["gelu_bwd8"], new["gelu_bwd8_act0"])
+        same("second launch differs", new, run())
+        # another shape in between: other tile counts, other descriptors, other LDS contents left behind
+        o.gemm_nt(a2, b2, bias2, **kw)
+        o.gemm_nt(a2, b2, bias2, epi=o.EPI_ACT, act=1, want_pre="e4m3", **kw)
+        o.gemm_nt(a2, b2, None, epi=o.EPI_DACT, act=2, aux=o.gemm_nt(a2, b2, bias2, epi=o.EPI_ACT, act=1, want_pre="e4m3", **kw)[1], want_act=True, **kw)
+        assert _last_gemm() == NTA
+        same("differs after a launch of another shape", new, run())
+        if name == "S1":
+            for sched in (0, 3, 4):                         # tools/gen_gemm_nta.py: SCHEDULES
+                _debug_set(2 + sched, 0)
+                lib.gemm_counts(reset=True)
+                alt = run()
+                assert lib.gemm_counts()[2] == 12
+                same(f"schedule {sched} differs from the default", new, alt)
+            for gm in (2, 5, 16):                           # flag bits 20..25: tile-group override (another order of the same tiles)
+                _debug_set(0, gm << 20)
+                lib.gemm_counts(reset=True)
+                alt = run()
+                assert lib.gemm_counts()[2] == 12
+                same(f"tile groups of {gm} panels change values", new, alt)
+    finally:
+        _debug_set(0, 0)
+    del old, a2, b2, bias2
+
+    # fp64: the product on the CPU, the element-wise references in fp64 torch on the device
+    if name == "S3":
+        panels = TW.panels_to_check(w)
+        assert len(panels) >= 8
+        rows = torch.cat([torch.arange(256 * p, 256 * p + 256) for p in panels])
+    else:
+        rows = torch.arange(M)
+    lin = (a[rows].double() @ b.double().T * 0.5 + bias.double()).to(DEV)
+    rows = rows.to(DEV)
+    v = lin.to(bf16).double()                                   # the GEMM result is rounded to bf16 before the epilogue
+    aux, hb = AUX[rows].double(), HB[rows].double()
+    check_dev("bias", new["bias"][rows], lin, 2 ** -7, 2e-3)
+    check_dev("pre", new["pre"][rows], lin, 2 ** -7, 2e-3)
+    pre = new["pre"][rows].double()
+    for act in (0, 1, 2):
+        check_dev(f"act {act}", new[f"act{act}"][rows], ref_act(pre, act), 2 ** -7, 2e-3)
+        check_dev(f"gelu backward from e4m3, act {act}", new[f"gelu_bwd8_act{act}"][rows], v * act_grad(hb, act), 2 ** -6, 6e-3)
+    check_dev("residual", new["residual"][rows], v + aux, 2 ** -7, 1.6e-2)
+    check_dev("gelu backward", new["gelu_bwd"][rows], v * act_grad(aux, 0), 2 ** -6, 6e-3)
+
+
+def test_gemm_nt2_ragged_shape_past_one_tile_per_workgroup():
+    """The kernel every shape can fall back to (gemm_nt2), ragged in M, N and K, with 603 tiles: two and three per workgroup.  The
+    epilogues and tolerances of test_gemm_nt_ragged_shapes_every_epilogue, every element against fp64, tile-dependent magnitudes."""
+    o = ops()
+    M, N, K = TW.RAGGED_BF16
+    w = TW.walk(M, N, K, 2, num_cu())
+    TW.require_second_tiles(w, f"gemm_nt2 {(M, N, K)} on {num_cu()} CUs")
+    a, b, bias = tile_scaled_operands(M, N, K, seed=11)
+    b = (b.float() * 0.5).to(bf16)                              # (no alpha here: unit variance times the factors again)
+    ad, bd, biasd = a.to(DEV), b.to(DEV), bias.to(DEV)
+    auxd = torch.randn(M, N, generator=torch.Generator(device=DEV).manual_seed(4), device=DEV, dtype=f32).to(bf16)
+    lin = (a.double() @ b.double().T + bias.double()).to(DEV)
+    prev = None
+    for rep in range(2):
+        got = [o.gemm_nt(ad, bd, biasd), o.gemm_nt(ad, bd, biasd, epi=o.EPI_ADD, aux=auxd)]
+        assert _last_gemm() == NT2
+        got += list(o.gemm_nt(ad, bd, biasd, epi=o.EPI_ACT, act=0, want_pre=True))
+        got.append(o.gemm_nt(ad, bd, biasd, epi=o.EPI_ACT, act=0))
+        assert torch.equal(got[2], got[4]), "activation epilogue with / without the pre-activation copy"
+        if prev is not None:
+            assert all(torch.equal(x, y) for x, y in zip(prev, got)), "second launch differs"
+        prev = got
+    check_dev("bias", got[0], lin, 2 ** -7, 2e-3)
+    check_dev("residual", got[1], lin + auxd.double(), 2 ** -6, 2e-2)   # two bf16 roundings
+    check_dev("pre", got[3], lin, 2 ** -7, 2e-3)
+    check_dev("gelu", got[2], ref_act(got[3].double(), 0), 2 ** -7, 2e-3)
 
 
 @pytest.mark.parametrize("M,N,K", [(1024, 768, 512), (512, 1024, 256), (1000, 520, 776)])
