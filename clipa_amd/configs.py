@@ -43,6 +43,10 @@ def _builtin():
     cfgs["ViT-L-16-CL32-GAP"] = _vit("L", 16, ctx=32, gap=True)
     cfgs["ViT-H-14-CL8-SyntaxMask-GAP"] = _vit("H", 14, ctx=8, gap=True, text_mask="syntax")
     cfgs["ViT-H-14-CL32-GAP"] = _vit("H", 14, ctx=32, gap=True)
+    # model_configs/ViT-M-16-alt.json: the ViT-M/16 image tower with LayerScale (transformer.py:43-50) beside a 384-wide text tower
+    cfgs["ViT-M-16-alt"] = {"embed_dim": 384,
+                            "vision_cfg": {"image_size": 224, "layers": 12, "width": 512, "patch_size": 16, "ls_init_value": 1e-4},
+                            "text_cfg": {"context_length": 77, "vocab_size": 49408, "width": 384, "heads": 6, "layers": 12}}
     # the reference's largest towers (model_configs/ViT-g-14.json, ViT-bigG-14.json - CLIPA-v2's G/14 -, ViT-e-14.json):
     # head widths 88 / 104 / 112, fractional mlp_ratio (MLP widths 6144 / 8192 / 15360)
     for name, (e, w, layers, hw, mlp, tw, th, tl) in {

@@ -721,3 +721,136 @@ extern "C" int clipa_sum_scale(const float* in, float* out, int64_t n, float sca
   hipLaunchKernelGGL(sum_scale_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, in, out, (long)n, scale, accumulate);
   return clipa_check_launch("sum_scale");
 }
+
+// ------------------------------------------------------------------------------------------------
+// LayerScale (open_clip/transformer.py:43-50, applied at :248-249): x + gamma * (a W^T + b) == x + a (diag(gamma) W)^T + gamma * b,
+// so the per-channel scale is FOLDED into the rows of the weight once per optimizer step and every GEMM launch stays as it is.
+// One wave per row of W [N,K]; 16-byte accesses when the rows are 16-byte aligned (K % 8 == 0 and aligned bases), else scalar.
+namespace {
+// 8 consecutive elements of a bf16 / f32 row as floats
+template <bool F32>
+__device__ __forceinline__ void ls_load8(const void* __restrict__ row, int k, float* v) {
+  if (F32) {
+    *(float4*)v = *(const float4*)((const float*)row + k);
+    *(float4*)(v + 4) = *(const float4*)((const float*)row + k + 4);
+  } else {
+    unpack8(*(const u32x4*)((const unsigned short*)row + k), v);
+  }
+}
+template <bool F32>
+__device__ __forceinline__ float ls_load1(const void* __restrict__ row, int k) {
+  return F32 ? ((const float*)row)[k] : bf2f(((const unsigned short*)row)[k]);
+}
+
+// wf[n,:] = bf16(gamma[n] * w[n,:]) (fp32 product, one rounding); bf[n] = gamma[n] * b[n]
+template <bool W_F32>
+__global__ __launch_bounds__(256) void layerscale_fold_kernel(const void* __restrict__ w, const float* __restrict__ gamma,
+                                                              const float* __restrict__ b, unsigned short* __restrict__ wf,
+                                                              float* __restrict__ bf, long N, int K, int kvec) {
+  const int lane = threadIdx.x & 63;
+  const long n = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const float g = gamma[n];
+  const void* row = W_F32 ? (const void*)((const float*)w + (size_t)n * K) : (const void*)((const unsigned short*)w + (size_t)n * K);
+  unsigned short* out = wf + (size_t)n * K;
+  for (int k = lane * 8; k < kvec; k += 64 * 8) {
+    float v[8];
+    ls_load8<W_F32>(row, k, v);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] *= g;
+    *(u32x4*)(out + k) = pack8(v);
+  }
+  for (int k = kvec + lane; k < K; k += 64) out[k] = f2bf(ls_load1<W_F32>(row, k) * g);
+  if (lane == 0) bf[n] = g * b[n];
+}
+
+// The parameters' gradients from the folded layer's: dw[n,:] = gamma[n] * dwf[n,:], db[n] = gamma[n] * dbf[n],
+// dgamma[n] = sum_k dwf[n,k] * w[n,k] + dbf[n] * b[n].  The row dot product is taken in fp32: every lane sums its elements in
+// ascending k, then the 64 partial sums meet in the fixed butterfly of wave_sum - no atomics, the same bits on every run.
+// Null dw / db / dgamma: that store (and, for dgamma, the read of w) is skipped.
+template <bool W_F32, bool DW_F32>
+__global__ __launch_bounds__(256) void layerscale_unfold_kernel(const float* __restrict__ dwf, const void* __restrict__ w,
+                                                                const float* __restrict__ gamma, const float* __restrict__ dbf,
+                                                                const float* __restrict__ b, void* __restrict__ dw,
+                                                                float* __restrict__ db, float* __restrict__ dgamma, long N, int K,
+                                                                int kvec) {
+  const int lane = threadIdx.x & 63;
+  const long n = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const float g = gamma[n];
+  const float* drow = dwf + (size_t)n * K;
+  const void* row = W_F32 ? (const void*)((const float*)w + (size_t)n * K) : (const void*)((const unsigned short*)w + (size_t)n * K);
+  float acc = 0.f;
+  for (int k = lane * 8; k < kvec; k += 64 * 8) {
+    float d[8];
+    ls_load8<true>(drow, k, d);
+    if (dgamma) {
+      float v[8];
+      ls_load8<W_F32>(row, k, v);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc += d[i] * v[i];
+    }
+    if (dw) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) d[i] *= g;
+      if (DW_F32) {
+        float* o = (float*)dw + (size_t)n * K + k;
+        *(float4*)o = make_float4(d[0], d[1], d[2], d[3]);
+        *(float4*)(o + 4) = make_float4(d[4], d[5], d[6], d[7]);
+      } else {
+        *(u32x4*)((unsigned short*)dw + (size_t)n * K + k) = pack8(d);
+      }
+    }
+  }
+  for (int k = kvec + lane; k < K; k += 64) {
+    const float d = drow[k];
+    if (dgamma) acc += d * ls_load1<W_F32>(row, k);
+    if (dw) {
+      if (DW_F32) ((float*)dw)[(size_t)n * K + k] = d * g;
+      else ((unsigned short*)dw)[(size_t)n * K + k] = f2bf(d * g);
+    }
+  }
+  if (dgamma) {
+    acc = wave_sum(acc);
+    if (lane == 0) dgamma[n] = acc + dbf[n] * b[n];
+  }
+  if (lane == 0 && db) db[n] = g * dbf[n];
+}
+
+// elements of a row the 16-byte path may take: all of them when every row starts 16-byte aligned, else none
+inline int ls_kvec(int64_t K, const void* a, const void* b, const void* c) {
+  const bool aligned = (((size_t)a | (size_t)b | (size_t)c) & 15) == 0;
+  return (K % 8 == 0 && aligned) ? (int)K : 0;
+}
+}  // namespace
+
+extern "C" int clipa_layerscale_fold(const void* w, int w_f32, const float* gamma, const float* b, void* w_folded,
+                                     float* b_folded, int64_t N, int64_t K, void* stream) {
+  if (!w || !gamma || !b || !w_folded || !b_folded) { clipa_set_error("layerscale_fold: null operand"); return CLIPA_ERR_ARG; }
+  if (N <= 0) return CLIPA_OK;
+  if (K <= 0 || K > 0x7fffffffL) { clipa_set_error("layerscale_fold: K=%ld outside [1, 2^31)", (long)K); return CLIPA_ERR_ARG; }
+  const int kvec = ls_kvec(K, w, w_folded, nullptr);
+  const dim3 grid((unsigned)((N + 3) / 4));
+  hipStream_t st = (hipStream_t)stream;
+  if (w_f32) hipLaunchKernelGGL(layerscale_fold_kernel<true>, grid, dim3(256), 0, st, w, gamma, b, (unsigned short*)w_folded, b_folded, (long)N, (int)K, kvec);
+  else hipLaunchKernelGGL(layerscale_fold_kernel<false>, grid, dim3(256), 0, st, w, gamma, b, (unsigned short*)w_folded, b_folded, (long)N, (int)K, kvec);
+  return clipa_check_launch("layerscale_fold");
+}
+
+extern "C" int clipa_layerscale_unfold(const float* dw_folded, const void* w, int w_f32, const float* gamma,
+                                       const float* db_folded, const float* b, void* dw, int dw_f32, float* db,
+                                       float* dgamma, int64_t N, int64_t K, void* stream) {
+  if (!dw_folded || !w || !gamma || !db_folded || !b) { clipa_set_error("layerscale_unfold: null operand (only the outputs dw, db, dgamma may be null)"); return CLIPA_ERR_ARG; }
+  if (N <= 0 || (!dw && !db && !dgamma)) return CLIPA_OK;
+  if (K <= 0 || K > 0x7fffffffL) { clipa_set_error("layerscale_unfold: K=%ld outside [1, 2^31)", (long)K); return CLIPA_ERR_ARG; }
+  const int kvec = ls_kvec(K, dw_folded, w, dw);
+  const dim3 grid((unsigned)((N + 3) / 4));
+  hipStream_t st = (hipStream_t)stream;
+#define CLIPA_LS_UNFOLD(WF, DF) hipLaunchKernelGGL((layerscale_unfold_kernel<WF, DF>), grid, dim3(256), 0, st, dw_folded, w, gamma, db_folded, b, dw, db, dgamma, (long)N, (int)K, kvec)
+  if (w_f32 && dw_f32) CLIPA_LS_UNFOLD(true, true);
+  else if (w_f32) CLIPA_LS_UNFOLD(true, false);
+  else if (dw_f32) CLIPA_LS_UNFOLD(false, true);
+  else CLIPA_LS_UNFOLD(false, false);
+#undef CLIPA_LS_UNFOLD
+  return clipa_check_launch("layerscale_unfold");
+}

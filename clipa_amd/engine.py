@@ -3,6 +3,7 @@ backward are sequences of HIP launches (clipa_amd.ops).  Mirrors, per function, 
 it stands in for (paths relative to /root/reference/clipa_torch):
 
   ResBlockFn     ResidualAttentionBlock.forward            open_clip/transformer.py:238-250
+                 (LayerScale, transformer.py:43-50, folded into out_proj / c_proj: _fold_layerscale)
   LastBlockFn    the same for a tower's last block when the head reads one row per sample (returns those rows only)
   VisionStemFn   conv1 + cls/pos + ln_pre                  open_clip/transformer.py:480-503
   TokenDropFn    PatchDropout (row selection)              open_clip/transformer.py:53-83,501-502
@@ -56,6 +57,18 @@ class WeightCache:
 
     def custom(self, p, kind, make):
         return self._get(p, kind, make)
+
+    def multi(self, ps, kind, make):
+        """An operand built from SEVERAL parameters (a LayerScale fold: weight, bias and gamma): valid while every one of them
+        is the same object with the same version counter and storage address.  make(*detached tensors)."""
+        key = (tuple(id(p) for p in ps), kind)
+        state = tuple((p._version, p.data_ptr()) for p in ps)
+        ent = self._c.get(key)
+        if ent is None or ent[0] != state or any(r() is not p for r, p in zip(ent[2], ps)):
+            with torch.no_grad():
+                ent = (state, make(*[p.detach() for p in ps]), tuple(weakref.ref(p) for p in ps))
+            self._c[key] = ent
+        return ent[1]
 
     def clear(self):
         self._c.clear()
@@ -306,8 +319,8 @@ def _block_backward_fp8(x, dy, box, P, cfg, scales, offer):
         cfg.handoff.offer(dx, q8, fmt)
     else:
         dx, d_ln1_w, d_ln1_b = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=dx1, eps=eps)
-    return dx, (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out, d_ln2_w, d_ln2_b, d_w_fc, d_b_fc, d_w_proj,
-                d_b_proj)
+    return dx, _unfold_layerscale(P, (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out, d_ln2_w, d_ln2_b, d_w_fc, d_b_fc,
+                                      d_w_proj, d_b_proj))
 
 
 def _block_backward(x, dy, box, P, cfg):
@@ -375,23 +388,61 @@ def _block_backward(x, dy, box, P, cfg):
         d_w_in, d_b_in = ops.gemm_tn(dqkv, h1, P["dt_w_in"], want_colsum=True)
         del dqkv, h1
         dx, d_ln1_w, d_ln1_b = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=dx1, eps=cfg.eps)
-    return dx, (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out, d_ln2_w, d_ln2_b, d_w_fc, d_b_fc, d_w_proj,
-                d_b_proj)
+    return dx, _unfold_layerscale(P, (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out, d_ln2_w, d_ln2_b, d_w_fc, d_b_fc,
+                                      d_w_proj, d_b_proj))
+
+
+def _fold_layerscale(P, cache, cfg, fp8_names, name, w, b, gamma):
+    """LayerScale (transformer.py:43-50: x + gamma * (a W^T + b), :248-249) of the layer `name` ("out" / "proj"), folded into its
+    operands: W' = diag(gamma) W and b' = gamma * b replace W and b in every operand form the block's launches read (forward,
+    transposed, fp8, the predicted scales' row norm), so no launch changes.  The folded copies live in the weight cache under
+    (W, b, gamma) together: a step of any of the three rebuilds them.  The layer's weight-gradient product is requested in f32:
+    it is dW' = dY^T X, from which _unfold_layerscale takes the parameters' gradients."""
+    ps = (w, b, gamma)
+    fold = lambda: cache.multi(ps, "ls", lambda wt, bt, gt: ops.layerscale_fold(wt, cache.f32(gamma), cache.f32(b)))
+    wT = lambda: cache.multi(ps, "ls_wt", lambda *t: ops.transpose_bf16(fold()[0]))
+    P["w_" + name], P["b_" + name] = fold()
+    P["wt_" + name] = wT()
+    P["dt_w_" + name] = f32
+    if cfg.fp8 and name in fp8_names:
+        P["w8_" + name] = cache.multi(ps, "ls_w8", lambda *t: ops.quantize_rows(fold()[0]))
+        P["wt8_" + name] = cache.multi(ps, "ls_wt8", lambda *t: ops.quantize_rows(wT()))
+        if cfg.predict and name == "proj" and "fc" in fp8_names:
+            P["wn_projT"] = cache.multi(ps, "ls_wnT", lambda *t: ops.rownorm_max(wT()))
+    return (name, w, b, gamma, cache.f32(gamma), cache.f32(b))
+
+
+def _unfold_layerscale(P, grads):
+    """Blocks with LayerScale: the gradients of the two folded layers (dW' in f32, db') become those of the parameters, dW =
+    diag(gamma) dW', db = gamma * db', plus dgamma = rowsum(dW' * W) + db' * b (ops.layerscale_unfold); -> the block's gradient
+    tuple with d(ls_1.gamma), d(ls_2.gamma) appended.  A frozen parameter's gradient is not computed."""
+    if "ls" not in P:
+        return grads
+    grads = list(grads)
+    slot = {"out": (4, 5), "proj": (10, 11)}      # (weight, bias) of the layer in the gradient tuple
+    for name, w, b, gamma, gamma32, b32 in P["ls"]:
+        iw, ib = slot[name]
+        grads[iw], grads[ib], dg = ops.layerscale_unfold(grads[iw], w.detach(), gamma32, grads[ib], b32, out_dtype=w.dtype,
+                                                         want=(w.requires_grad, b.requires_grad, gamma.requires_grad))
+        grads.append(dg)
+    return tuple(grads)
 
 
 def _block_operands(params, cache, cfg, fp8_names=("in", "out", "fc", "proj")):
-    ln1_w, ln1_b, w_in, b_in, w_out, b_out, ln2_w, ln2_b, w_fc, b_fc, w_proj, b_proj = params
-    P = {
-        "ln1_w": cache.f32(ln1_w), "ln1_b": cache.f32(ln1_b), "ln2_w": cache.f32(ln2_w), "ln2_b": cache.f32(ln2_b),
-        "w_in": cache.w(w_in), "w_out": cache.w(w_out), "w_fc": cache.w(w_fc), "w_proj": cache.w(w_proj),
-        "wt_in": cache.wt(w_in), "wt_out": cache.wt(w_out), "wt_fc": cache.wt(w_fc), "wt_proj": cache.wt(w_proj),
-        "b_in": cache.f32(b_in), "b_out": cache.f32(b_out), "b_fc": cache.f32(b_fc), "b_proj": cache.f32(b_proj),
-        "dt_w_in": w_in.dtype, "dt_w_out": w_out.dtype, "dt_w_fc": w_fc.dtype, "dt_w_proj": w_proj.dtype,
-    }
+    """params: _ResBlockParams.param_tuple() - twelve tensors, and the two LayerScale gammas behind them when the block has any."""
+    ln1_w, ln1_b, w_in, b_in, w_out, b_out, ln2_w, ln2_b, w_fc, b_fc, w_proj, b_proj = params[:12]
+    layers = (("in", w_in, b_in), ("out", w_out, b_out), ("fc", w_fc, b_fc), ("proj", w_proj, b_proj))
+    # layers whose operands are the LayerScale-folded ones (_fold_layerscale) instead of the parameter's own copies
+    folded = {"out": params[12], "proj": params[13]} if len(params) > 12 else {}
+    P = {"ln1_w": cache.f32(ln1_w), "ln1_b": cache.f32(ln1_b), "ln2_w": cache.f32(ln2_w), "ln2_b": cache.f32(ln2_b)}
+    P.update({"w_" + name: cache.w(w) for name, w, _ in layers if name not in folded})
+    P.update({"wt_" + name: cache.wt(w) for name, w, _ in layers if name not in folded})
+    P.update({"b_" + name: cache.f32(b) for name, _, b in layers if name not in folded})
+    P.update({"dt_w_" + name: w.dtype for name, w, _ in layers if name not in folded})
     if cfg.fp8:   # e4m3 copies, one scale per output channel of the GEMM they feed (rows of W forward, rows of W^T backward); only
         # of the layers that run on the fp8 path (LastBlockFn: the in-projection alone - its B pooled rows take the bf16 GEMMs)
-        for name, w in (("in", w_in), ("out", w_out), ("fc", w_fc), ("proj", w_proj)):
-            if name not in fp8_names:
+        for name, w, _ in layers:
+            if name not in fp8_names or name in folded:
                 continue
             P["w8_" + name] = cache.custom(w, "w8", lambda t, w=w: ops.quantize_rows(cache.w(w)))
             P["wt8_" + name] = cache.custom(w, "wt8", lambda t, w=w: ops.quantize_rows(cache.wt(w)))
@@ -401,7 +452,11 @@ def _block_operands(params, cache, cfg, fp8_names=("in", "out", "fc", "proj")):
             # gradient that comes back through c_proj; device scalars, refreshed with the operand copies once per optimizer step
             P["wn_fc"] = cache.custom(w_fc, "wn", lambda t: ops.rownorm_max(cache.w(w_fc)))
             P["bmax_fc"] = cache.custom(b_fc, "bmax", lambda t: ops.absmax(cache.f32(b_fc)))
-            P["wn_projT"] = cache.custom(w_proj, "wnT", lambda t: ops.rownorm_max(cache.wt(w_proj)))
+            if "proj" not in folded:
+                P["wn_projT"] = cache.custom(w_proj, "wnT", lambda t: ops.rownorm_max(cache.wt(w_proj)))
+    if folded:
+        P["ls"] = tuple(_fold_layerscale(P, cache, cfg, fp8_names, name, w, b, folded[name]) for name, w, b in layers
+                        if name in folded)
     return P
 
 
@@ -533,7 +588,8 @@ class LastBlockFn(torch.autograd.Function):
             del dqkv, h1
         # x1 = x[rows] + out_proj(a[rows]): the residual gradient reaches x at the pooled rows only
         dx, d_ln1_w, d_ln1_b = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=ops.scatter_rows(dx1, rows, M), eps=cfg.eps)
-        grads = (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out, d_ln2_w, d_ln2_b, d_w_fc, d_b_fc, d_w_proj, d_b_proj)
+        grads = _unfold_layerscale(P, (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out, d_ln2_w, d_ln2_b, d_w_fc, d_b_fc,
+                                       d_w_proj, d_b_proj))
         grads = tuple(_like_param(gr, p) if p.requires_grad else None for gr, p in zip(grads, params))
         return (dx, None, None, None) + grads
 

@@ -57,6 +57,8 @@ SIGNATURES = {
     "clipa_cast_to_bf16": (_I32, [_P, _I32, _P, _I64, _P]),
     "clipa_cast_bf16_to_f32": (_I32, [_P, _P, _I64, _P]),
     "clipa_transpose_to_bf16": (_I32, [_P, _I32, _P, _I64, _I64, _I64, _I64, _P]),
+    "clipa_layerscale_fold": (_I32, [_P, _I32, _P, _P, _P, _P, _I64, _I64, _P]),
+    "clipa_layerscale_unfold": (_I32, [_P, _P, _I32, _P, _P, _P, _P, _I32, _P, _P, _I64, _I64, _P]),
     "clipa_activation_fwd": (_I32, [_P, _P, _I64, _I32, _P]),
     "clipa_cast_bf16_to_e4m3": (_I32, [_P, _P, _I64, _P]),
     "clipa_cast_e4m3_to_bf16": (_I32, [_P, _P, _I64, _P]),

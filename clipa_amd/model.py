@@ -112,24 +112,44 @@ def _unsupported(what):
                               "use the reference implementation for it")
 
 
-class _ResBlockParams(nn.Module):
-    """Parameter holder with the names of ResidualAttentionBlock (transformer.py:195-221)."""
+class _LayerScaleParams(nn.Module):
+    """Parameter holder with the name of LayerScale (transformer.py:43-50): `gamma`, one scale per channel."""
 
-    def __init__(self, d_model, n_head, mlp_ratio=4.0):
+    def __init__(self, dim, init_values):
+        super().__init__()
+        self.gamma = nn.Parameter(init_values * torch.ones(dim))
+
+    def forward(self, *a, **k):
+        raise RuntimeError("parameter holder: folded into the block's GEMM operands by clipa_amd.engine")
+
+
+class _ResBlockParams(nn.Module):
+    """Parameter holder with the names of ResidualAttentionBlock (transformer.py:195-221).  ls_init_value: the block scales its
+    two branches by learnable per-channel factors ls_1.gamma / ls_2.gamma (transformer.py:210,221,248-249); None: no such
+    modules, parameters or state_dict keys (the reference holds nn.Identity there)."""
+
+    def __init__(self, d_model, n_head, mlp_ratio=4.0, ls_init_value=None):
         super().__init__()
         self.ln_1 = nn.LayerNorm(d_model)
         self.attn = nn.MultiheadAttention(d_model, n_head)
+        if ls_init_value is not None:
+            self.ls_1 = _LayerScaleParams(d_model, ls_init_value)
         self.ln_2 = nn.LayerNorm(d_model)
         mlp_width = int(d_model * mlp_ratio)
         self.mlp = nn.Sequential(OrderedDict([
             ("c_fc", nn.Linear(d_model, mlp_width)),
             ("c_proj", nn.Linear(mlp_width, d_model)),
         ]))
+        if ls_init_value is not None:
+            self.ls_2 = _LayerScaleParams(d_model, ls_init_value)
+        self.layer_scale = ls_init_value is not None
 
     def param_tuple(self):
-        return (self.ln_1.weight, self.ln_1.bias, self.attn.in_proj_weight, self.attn.in_proj_bias,
+        """The block's tensors in the order engine._block_operands reads them; blocks with LayerScale append their two gammas."""
+        base = (self.ln_1.weight, self.ln_1.bias, self.attn.in_proj_weight, self.attn.in_proj_bias,
                 self.attn.out_proj.weight, self.attn.out_proj.bias, self.ln_2.weight, self.ln_2.bias,
                 self.mlp.c_fc.weight, self.mlp.c_fc.bias, self.mlp.c_proj.weight, self.mlp.c_proj.bias)
+        return base + (self.ls_1.gamma, self.ls_2.gamma) if self.layer_scale else base
 
     def forward(self, *a, **k):
         raise RuntimeError("parameter holder: computed by clipa_amd.engine.ResBlockFn")
@@ -151,7 +171,7 @@ KEEP_SETS = {"light": frozenset(("qkv", "a", "x1", "h")), "light8": frozenset(("
 class Transformer(nn.Module):
     """transformer.py:294-326: a stack of residual attention blocks over a [B*L, D] token matrix."""
 
-    def __init__(self, width, layers, heads, mlp_ratio=4.0, act=ops.ACT_GELU_ERF):
+    def __init__(self, width, layers, heads, mlp_ratio=4.0, act=ops.ACT_GELU_ERF, ls_init_value=None):
         super().__init__()
         if width % heads != 0 or width // heads not in (64, 80, 88, 104, 112):
             _unsupported(f"head dim {width // heads if heads else '?'} (the fused attention kernels cover 64, 80 and - image "
@@ -182,7 +202,7 @@ class Transformer(nn.Module):
         # e4m3 operands with PREDICTED row scales (a Cauchy-Schwarz bound from the producer's row norm and the weight's largest
         # row norm) instead of bf16 + a row quantiser: ~5 % faster, per-tensor gradient cosines 0.001-0.009 lower
         self.fp8_predicted_scales = False
-        self.resblocks = nn.ModuleList([_ResBlockParams(width, heads, mlp_ratio) for _ in range(layers)])
+        self.resblocks = nn.ModuleList([_ResBlockParams(width, heads, mlp_ratio, ls_init_value) for _ in range(layers)])
         self._handoff = engine.GradHandoff()      # the fp8 blocks' gradient-operand slot (one per tower)
 
     def get_cast_dtype(self):
@@ -245,7 +265,7 @@ class VisionTransformer(nn.Module):
 
     def __init__(self, image_size, patch_size, width, layers, heads, mlp_ratio, output_dim, global_average_pool=False,
                  act=ops.ACT_GELU_ERF, pos_embed='learnable', ln_pre=True, pool_style='open_clip', cache=None,
-                 patch_dropout=0.):
+                 patch_dropout=0., ls_init_value=None):
         super().__init__()
         assert 0 <= patch_dropout < 1.
         self.patch_dropout = float(patch_dropout)      # transformer.py:386-388 (0 = disabled)
@@ -268,7 +288,7 @@ class VisionTransformer(nn.Module):
         else:
             raise NotImplementedError(pos_embed)
         self.ln_pre = nn.LayerNorm(width) if ln_pre else nn.Identity()
-        self.transformer = Transformer(width, layers, heads, mlp_ratio, act=act)
+        self.transformer = Transformer(width, layers, heads, mlp_ratio, act=act, ls_init_value=ls_init_value)
         self.global_average_pool = global_average_pool
         self.attn_pool = None
         self.ln_post = nn.LayerNorm(width)
@@ -359,9 +379,8 @@ class CLIP(nn.Module):
             text_cfg = CLIPTextCfg(**text_cfg)
         if vision_cfg.timm_model_name or isinstance(vision_cfg.layers, (tuple, list)):
             _unsupported("timm / ResNet vision towers")
-        if vision_cfg.attentional_pool or vision_cfg.input_patchnorm or \
-                vision_cfg.ls_init_value is not None or text_cfg.ls_init_value is not None:
-            _unsupported("attentional pool / patchnorm / layer scale")
+        if vision_cfg.attentional_pool or vision_cfg.input_patchnorm:
+            _unsupported("attentional pool / patchnorm")
         if text_cfg.hf_model_name or text_cfg.embed_cls:
             _unsupported("HF text towers / embed_cls")
         self._cache = engine.WeightCache()
@@ -376,10 +395,11 @@ class CLIP(nn.Module):
             output_dim=embed_dim, global_average_pool=vision_cfg.global_average_pool,
             act=_act_code(quick_gelu, vision_cfg.gelu_approximate), pos_embed=vision_cfg.pos_embed,
             ln_pre=vision_cfg.ln_pre, pool_style=vision_cfg.pool_style, cache=self._cache,
-            patch_dropout=vision_cfg.patch_dropout)
+            patch_dropout=vision_cfg.patch_dropout, ls_init_value=vision_cfg.ls_init_value)
         # text tower: sub-modules live directly on CLIP (model.py:216-225)
         self.transformer = Transformer(text_cfg.width, text_cfg.layers, text_cfg.heads,
-                                       act=_act_code(quick_gelu, text_cfg.gelu_approximate))
+                                       act=_act_code(quick_gelu, text_cfg.gelu_approximate),
+                                       ls_init_value=text_cfg.ls_init_value)
         self.context_length = text_cfg.context_length
         self.vocab_size = text_cfg.vocab_size
         self.token_embedding = nn.Embedding(text_cfg.vocab_size, text_cfg.width)

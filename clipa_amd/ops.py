@@ -907,6 +907,57 @@ def transpose_bf16(t):
     return out
 
 
+def _chk_layerscale(w, gamma, b, who):
+    if w.dtype not in (f32, bf16):
+        raise RuntimeError(f"clipa_amd.ops.{who}: w must be torch.float32 or torch.bfloat16, got {w.dtype}")
+    _chk(w, None, "w", 2)
+    _chk(gamma, f32, "gamma", 1)
+    N = w.shape[0]
+    if gamma.shape[0] != N:
+        raise RuntimeError(f"clipa_amd.ops.{who}: gamma has {gamma.shape[0]} entries for {N} rows of w")
+    _chk(b, f32, "b", 1)
+    if b.shape[0] != N:
+        raise RuntimeError(f"clipa_amd.ops.{who}: b has {b.shape[0]} entries for {N} rows of w")
+
+
+def layerscale_fold(w, gamma, b):
+    """LayerScale folded into the layer it scales (transformer.py:43-50,248-249): w [N,K] f32/bf16, gamma / b f32 [N] ->
+    (bf16 [N,K] = bf16(gamma[:,None] * w), f32 [N] = gamma * b); fp32 product, one rounding."""
+    _chk_layerscale(w, gamma, b, "layerscale_fold")
+    w, gamma, b = w.contiguous(), gamma.contiguous(), b.contiguous()
+    N, K = w.shape
+    wf = torch.empty((N, K), device=w.device, dtype=bf16)
+    bf = torch.empty(N, device=w.device, dtype=f32)
+    with _Timed("layerscale_fold", 0.0, float(N) * K * (w.element_size() + 2)):
+        lib.call("clipa_layerscale_fold", _p(w), int(w.dtype == f32), _p(gamma), _p(b), _p(wf), _p(bf), N, K, _stream())
+    return wf, bf
+
+
+def layerscale_unfold(dwf, w, gamma, dbf, b, out_dtype=f32, want=(True, True, True)):
+    """The parameters' gradients of a layer that ran with folded LayerScale: dwf f32 [N,K] and dbf f32 [N] are the folded layer's
+    weight and bias gradients -> (dw [N,K] in out_dtype = gamma[:,None] * dwf, db f32 = gamma * dbf, dgamma f32 [N] =
+    sum_k dwf * w + dbf * b; fp32, fixed order).  want: which of the three to compute (None in place of the others)."""
+    _chk_out_dtype(out_dtype, "layerscale_unfold")
+    _chk_layerscale(w, gamma, b, "layerscale_unfold")
+    _chk(dwf, f32, "dwf", 2)
+    if dwf.shape != w.shape:
+        raise RuntimeError(f"clipa_amd.ops.layerscale_unfold: dwf {tuple(dwf.shape)} vs w {tuple(w.shape)}")
+    _chk(dbf, f32, "dbf", 1)
+    if dbf.shape[0] != w.shape[0]:
+        raise RuntimeError(f"clipa_amd.ops.layerscale_unfold: dbf has {dbf.shape[0]} entries for {w.shape[0]} rows of w")
+    want_w, want_b, want_g = (bool(v) for v in want)
+    dwf, w, gamma, dbf, b = dwf.contiguous(), w.contiguous(), gamma.contiguous(), dbf.contiguous(), b.contiguous()
+    N, K = w.shape
+    dw = torch.empty((N, K), device=w.device, dtype=out_dtype) if want_w else None
+    db = torch.empty(N, device=w.device, dtype=f32) if want_b else None
+    dg = torch.empty(N, device=w.device, dtype=f32) if want_g else None
+    with _Timed("layerscale_unfold", 2.0 * N * K if want_g else 0.0,
+                float(N) * K * (4 + (w.element_size() if want_g else 0) + (dw.element_size() if want_w else 0))):
+        lib.call("clipa_layerscale_unfold", _p(dwf), _p(w), int(w.dtype == f32), _p(gamma), _p(dbf), _p(b), _p(dw),
+                 int(out_dtype == f32), _p(db), _p(dg), N, K, _stream())
+    return dw, db, dg
+
+
 def activation_fwd(x, act):
     """bf16 act(x) (gelu erf / tanh / quick); x bf16, or e4m3 bytes (uint8: the "light8" keep tier's pre-activation)."""
     if x.dtype == u8:

@@ -265,6 +265,19 @@ int clipa_cast_to_bf16(const void* in, int in_f32, void* out, int64_t n, void* s
 int clipa_cast_bf16_to_f32(const void* in, float* out, int64_t n, void* stream);
 int clipa_transpose_to_bf16(const void* in, int in_f32, void* out, int64_t R, int64_t C, int64_t ldi,
                             int64_t ldo, void* stream);
+/* LayerScale (open_clip/transformer.py:43-50, applied at :248-249: x + gamma * (a W^T + b)) folded into the layer it scales,
+ * so that the GEMMs run unchanged on W' = diag(gamma) W and b' = gamma * b.  w [N,K] bf16 or f32 (w_f32), gamma / b f32 [N].
+ * fold:   w_folded [N,K] bf16 = bf16(gamma[n] * w[n,k]) (fp32 product, one rounding), b_folded f32 [N] = gamma * b.
+ * unfold: from dw_folded f32 [N,K] = dY^T X and db_folded f32 [N] = colsum(dY) of the folded layer:
+ *         dw [N,K] (f32 if dw_f32, else bf16) = gamma[n] * dw_folded[n,k], db f32 = gamma * db_folded,
+ *         dgamma f32 [N] = sum_k dw_folded[n,k] * w[n,k] + db_folded[n] * b[n]  (fp32, fixed summation order, no atomics).
+ *         A null dw / db / dgamma skips that output (frozen parameter).
+ * Any K: rows that are not 16-byte aligned (K % 8 != 0, unaligned bases) take a scalar path. */
+int clipa_layerscale_fold(const void* w, int w_f32, const float* gamma, const float* b, void* w_folded, float* b_folded,
+                          int64_t N, int64_t K, void* stream);
+int clipa_layerscale_unfold(const float* dw_folded, const void* w, int w_f32, const float* gamma, const float* db_folded,
+                            const float* b, void* dw, int dw_f32, float* db, float* dgamma, int64_t N, int64_t K,
+                            void* stream);
 /* out = act(in) elementwise, bf16 (MLP activation re-materialised from the kept pre-activation) */
 int clipa_activation_fwd(const void* in, void* out, int64_t n, int act, void* stream);
 /* Fused similarity + cross-entropy of the InfoNCE loss (loss.py:128-155): logits = s * rows . cols^T (rows [R,E],
