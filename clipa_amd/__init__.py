@@ -4,7 +4,8 @@ Public surface mirrors `open_clip` (clipa_torch/open_clip/__init__.py) for the V
 create_model, create_model_and_transforms, create_loss, CLIP, ClipLoss, DistillClipLoss, SigLipLoss,
 convert_weights_to_lp,
 get_cast_dtype, list_models, add_model_config; and the trainer's validation (training/train.py: evaluate,
-get_clip_metrics) and multi-caption image-text retrieval (`image_text_retrieval`, `evaluate_retrieval`).
+get_clip_metrics), multi-caption image-text retrieval (`image_text_retrieval`, `evaluate_retrieval`) and the few-shot
+linear probe (`fewshot_lsr`, `fewshot_metrics`, `evaluate_fewshot`).
 """
 from .configs import add_model_config, get_model_config, list_models
 from .factory import (create_loss, create_model, create_model_and_transforms, get_cast_dtype, load_checkpoint)
@@ -13,7 +14,9 @@ from .model import (CLIP, CLIPTextCfg, CLIPVisionCfg, OPENAI_DATASET_MEAN, OPENA
                     get_2d_sincos_pos_embed, resize_pos_embed, resize_text_pos_embed)
 
 from .data import DeviceAugment, DevicePrefetcher
+from . import fewshot
 from .evaluate import evaluate, get_clip_metrics, metrics_from_ranks
+from .fewshot import evaluate_fewshot, fewshot_lsr, fewshot_metrics
 from .retrieval_eval import evaluate_retrieval, image_text_retrieval
 from .transform import AugmentationCfg, image_transform
 from .zero import ShardedAdamW

@@ -91,6 +91,11 @@ SIGNATURES = {
     "clipa_retrieval_ranks": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "clipa_retrieval_ranks_multi_workspace": (_I64, [_I64, _I64]),
     "clipa_retrieval_ranks_multi": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "clipa_fewshot_moments": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _P]),
+    "clipa_fewshot_whiten": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _I64, _P, _I64, _P]),
+    "clipa_fewshot_gram": (_I32, [_P, _I64, _I64, _I64, _P, _I64, _P]),
+    "clipa_fewshot_class_sums": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _P, _I64, _P]),
+    "clipa_fewshot_predict": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P]),
     "clipa_adamw": (_I32, [_P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _F, _F, _F, _I64, _F, _P]),
     "clipa_adamw_multi": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _F, _F, _F, _F, _F, _I64, _F, _P, _I32, _F, _F, _P]),
     "clipa_grad_sqnorm_multi": (_I32, [_P, _P, _I32, _I32, _P, _P, _I64, _P]),

@@ -1161,6 +1161,117 @@ def retrieval_ranks_multi(img, txt, txt2img, scale=None):
     return oi[0, :Ni], oi[1, :Ni], t2i_gt, t2i_eq
 
 
+def _fewshot_rows(x, index, who, validate=True):
+    """x [Ntot, D] f32 and an optional row list -> (x with a 16-byte aligned base, ldx, int32 list | None, rows taken).  A
+    misaligned x is copied into a dense buffer (whose row stride is then D, whatever the view's was).  validate: check the
+    list's values here (one host sync); a caller that built the list on the host from valid rows passes an int32 tensor and
+    validate=False.  The kernels never dereference a bad value either (its row reads NaN)."""
+    _chk(x, f32, "x", 2)
+    x, ldx = _rowmajor(x)
+    if x.data_ptr() % 16:
+        x = x.clone(memory_format=torch.contiguous_format)
+        ldx = x.shape[1]
+    if index is None:
+        return x, ldx, None, x.shape[0]
+    if not torch.is_tensor(index) or not index.is_cuda or index.dim() != 1 or index.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError(f"{who}: index must be a 1-D int32 / int64 GPU tensor")
+    if validate and index.numel():
+        lo, hi = torch.stack([index.min(), index.max()]).tolist()
+        if lo < 0 or hi >= x.shape[0]:
+            raise RuntimeError(f"{who}: index values must lie in [0, {x.shape[0]}); got [{lo}, {hi}]")
+    return x, ldx, index.to(torch.int32).contiguous(), index.numel()
+
+
+def _vec16(t, n, name):
+    _chk(t, f32, name, 1)
+    if t.shape[0] != n:
+        raise RuntimeError(f"clipa_amd.ops: {name} must hold {n} values, got {t.shape[0]}")
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 16 else t
+
+
+def fewshot_moments(x, index=None, validate=True):
+    """Whitening statistics of the few-shot probe (fewshot_lsr.py:39-40) over rows `index` (int GPU tensor; None = all) of
+    x f32 [Ntot, D]: -> (mean [D], std [D]), std = sqrt(mean((x - mean)^2)) + 1e-5, two passes, a fixed summation order.
+    validate=False skips the range check of `index` (and its host sync) for a list the caller knows to be valid."""
+    x, ldx, index, N = _fewshot_rows(x, index, "fewshot_moments", validate)
+    D = x.shape[1]
+    if N < 1:
+        raise RuntimeError("fewshot_moments: needs at least one row")
+    out = torch.empty((2, (D + 3) // 4 * 4), device=x.device, dtype=f32)       # rows 16-byte aligned
+    with _Timed("fewshot_moments", 0.0, 8.0 * N * D):
+        lib.call("clipa_fewshot_moments", _p(x), _p(index), N, x.shape[0], D, ldx, _p(out[0]), _p(out[1]), _stream())
+    return out[0, :D], out[1, :D]
+
+
+def fewshot_whiten(x, mean, std, index=None, transpose=False, validate=True):
+    """z = (x[index] - mean) / std with the constant 100.0 column appended (fewshot_lsr.py:41-44, 95-96): -> Z, the [N, D + 1]
+    view of a [N, D + 1 rounded up to 4] buffer whose other columns are 0; with transpose=True -> (Z, Zt), Zt the [D + 1, N]
+    view of a [D + 1, N rounded up to 4] buffer padded the same way.  validate: as fewshot_moments."""
+    x, ldx, index, N = _fewshot_rows(x, index, "fewshot_whiten", validate)
+    D = x.shape[1]
+    mean, std = _vec16(mean, D, "mean"), _vec16(std, D, "std")
+    dim = D + 1
+    zb = torch.empty((N, (dim + 3) // 4 * 4), device=x.device, dtype=f32)
+    tb = torch.empty((dim, (N + 3) // 4 * 4), device=x.device, dtype=f32) if transpose else None
+    with _Timed("fewshot_whiten", 0.0, 4.0 * N * D * (3 if transpose else 2)):
+        lib.call("clipa_fewshot_whiten", _p(x), _p(index), N, x.shape[0], D, ldx, _p(mean), _p(std), _p(zb), zb.shape[1], _p(tb),
+                 tb.shape[1] if transpose else 0, _stream())
+    return (zb[:, :dim], tb[:, :N]) if transpose else zb[:, :dim]
+
+
+def fewshot_gram(a):
+    """S = a @ a^T for a f32 [M, E] in the fp32 arithmetic of the retrieval kernels (one ascending-k chain per entry); only the
+    upper 128 x 128 tiles are computed, their mirror images written: S == S^T bit for bit.  -> f32 [M, M]."""
+    _chk(a, f32, "a", 2)
+    a, lda = _aligned_rows(a)
+    M, E = a.shape
+    if E < 1:
+        raise RuntimeError("fewshot_gram: a has no columns")
+    S = torch.empty((M, M), device=a.device, dtype=f32)
+    with _Timed("fewshot_gram", 1.0 * M * M * E):
+        lib.call("clipa_fewshot_gram", _p(a), M, E, lda, _p(S), M, _stream())
+    return S
+
+
+def fewshot_class_sums(z, offsets):
+    """z^T y of the few-shot probe (fewshot_lsr.py:47, 74) for y = +1 at the label and -1 elsewhere, without y: z f32 [N, dim]
+    with its rows sorted by class, offsets the C + 1 segment bounds (host sequence or tensor: 0 = offsets[0] <= ... <=
+    offsets[C] = N).  -> R f32 [dim, C], R[d, c] = 2 * (sum of class c's rows) - (sum of all rows)."""
+    _chk(z, f32, "z", 2)
+    z, ldz = _aligned_rows(z)
+    N, dim = z.shape
+    off = [int(v) for v in (offsets.reshape(-1).tolist() if torch.is_tensor(offsets) else offsets)]
+    if len(off) < 2 or off[0] != 0 or off[-1] != N or any(b < a for a, b in zip(off, off[1:])):
+        raise RuntimeError(f"fewshot_class_sums: offsets must rise from 0 to N = {N} over at least one class; got "
+                           f"{off[:4]}...{off[-2:]}")
+    C = len(off) - 1
+    offs = torch.tensor(off, dtype=torch.int32).to(z.device)
+    R = torch.empty((dim, C), device=z.device, dtype=f32)
+    with _Timed("fewshot_class_sums", 0.0, 4.0 * (N * dim + 3 * dim * C)):
+        lib.call("clipa_fewshot_class_sums", _p(z), _p(offs), N, dim, C, ldz, _p(R), C, _stream())
+    return R
+
+
+def fewshot_predict(z, w):
+    """argmax over classes of z @ w^T (fewshot_lsr.py:107) without the [Nt, C] logits: z f32 [Nt, dim] whitened test rows,
+    w f32 [C, dim] class-major weights.  -> (pred int32 [Nt], best f32 [Nt]): the lowest class index among a row's maxima and
+    that logit."""
+    _chk(z, f32, "z", 2)
+    _chk(w, f32, "w", 2)
+    if z.shape[1] != w.shape[1] or w.shape[0] < 1 or w.shape[1] < 1:
+        raise RuntimeError(f"fewshot_predict: z {tuple(z.shape)} and w {tuple(w.shape)} must be [Nt, dim] and [C >= 1, dim >= 1]")
+    z, ldz = _aligned_rows(z)
+    w, ldw = _aligned_rows(w)
+    Nt, dim = z.shape
+    C = w.shape[0]
+    out_p = torch.empty((Nt + 3) // 4 * 4, device=z.device, dtype=torch.int32)
+    out_b = torch.empty((Nt + 3) // 4 * 4, device=z.device, dtype=f32)
+    with _Timed("fewshot_predict", 2.0 * Nt * C * dim):
+        lib.call("clipa_fewshot_predict", _p(z), _p(w), Nt, C, dim, ldz, ldw, _p(out_p), _p(out_b), _stream())
+    return out_p[:Nt], out_b[:Nt]
+
+
 def sum_scale(x, scale, out=None, accumulate=False):
     x = x.contiguous()
     if out is None:

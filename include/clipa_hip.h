@@ -353,6 +353,35 @@ int64_t clipa_retrieval_ranks_multi_workspace(int64_t Ni, int64_t Nt);
 int clipa_retrieval_ranks_multi(const float* A, const float* B, const int32_t* txt2img, int64_t Ni, int64_t Nt, int64_t E,
                                 int64_t lda, int64_t ldb, const float* scale, int32_t* i2t_gt, int32_t* i2t_eq,
                                 int32_t* t2i_gt, int32_t* t2i_eq, void* workspace, int64_t workspace_bytes, void* stream);
+/* Few-shot linear probe (clipa_jax/evaluators/fewshot_lsr.py, big_vision's closed-form L2-regularised least squares on frozen
+ * features).  Everything fp32; every reduction in a fixed order (no float atomics, results bit-reproducible); pointers 16-byte
+ * aligned (index 4), matrices row-major.  Zero-sized inputs return CLIPA_OK with the result of the empty computation: no
+ * output where there is nothing to write; moments over N = 0 rows gives mean = std = NaN (0 / 0, as numpy); gram over E = 0
+ * columns gives S = 0; predict over dim = 0 gives pred = 0, best = 0.  The one exception is predict with C = 0 classes for
+ * Nt > 0 rows, CLIPA_ERR_ARG: no argmax exists.
+ * moments (fewshot_lsr.py:39-40): over rows index[0..N) of x [Ntot, D] (index NULL: rows 0..N), mean[d] and
+ * std[d] = sqrt(mean((x - mean)^2)) + 1e-5 in two passes.  An index outside [0, Ntot) is never dereferenced (its row reads NaN). */
+int clipa_fewshot_moments(const float* x, const int32_t* index, int64_t N, int64_t Ntot, int64_t D, int64_t ldx, float* mean,
+                          float* std, void* stream);
+/* whiten (fewshot_lsr.py:41-44, 95-96): Z [N, ldz] = (x[index] - mean) / std (a true subtraction, then a true division), column
+ * D = 100.0 (BIAS_CONSTANT), columns (D, ldz) = 0; ldz >= D + 1.  Zt (optional) [D + 1, ldt] = the transpose, columns [N, ldt) = 0. */
+int clipa_fewshot_whiten(const float* x, const int32_t* index, int64_t N, int64_t Ntot, int64_t D, int64_t ldx,
+                         const float* mean, const float* std, float* Z, int64_t ldz, float* Zt, int64_t ldt, void* stream);
+/* gram (x.T @ x / x @ x.T of fewshot_lsr.py:72-79): S [M, lds] = A A^T for A [M, E] (lda >= E, a multiple of 4), one ascending-k
+ * fp32 fmaf chain per entry (the arithmetic of clipa_retrieval_ranks), the upper 128 x 128 tiles computed and mirrored:
+ * S == S^T bit for bit. */
+int clipa_fewshot_gram(const float* A, int64_t M, int64_t E, int64_t lda, float* S, int64_t lds, void* stream);
+/* class sums (x.T @ y of fewshot_lsr.py:47, 74 for y = +1 at the label, -1 elsewhere, y never formed): the rows of Z [N, ldz]
+ * sorted by class, offsets int32 [C + 1] in DEVICE memory (class c = rows [offsets[c], offsets[c + 1]), clamped to [0, N]);
+ * R [dim, ldr], R[d, c] = 2 sum_{n in c} Z[n, d] - sum_n Z[n, d]: segment sums in row order, their total in class order.
+ * C <= 65535. */
+int clipa_fewshot_class_sums(const float* Z, const int32_t* offsets, int64_t N, int64_t dim, int64_t C, int64_t ldz, float* R,
+                             int64_t ldr, void* stream);
+/* predict (jnp.argmax(x_test @ w, axis=1), fewshot_lsr.py:107) without the [Nt, C] logits: Z [Nt, ldz] whitened test rows,
+ * W [C, ldw] class-major weights (ldz, ldw >= dim, multiples of 4), logits by the arithmetic of clipa_fewshot_gram;
+ * pred[n] = the lowest class index among the maxima of row n, best[n] = that logit (finite logits assumed). */
+int clipa_fewshot_predict(const float* Z, const float* W, int64_t Nt, int64_t C, int64_t dim, int64_t ldz, int64_t ldw,
+                          int32_t* pred, float* best, void* stream);
 
 /* AdamW over one flat tensor (training/main.py:318-326 torch.optim.AdamW + train.py:285-286 clamp is
  * done by the caller): p -= lr*(m_hat/(sqrt(v_hat)+eps) + wd*p). param/grad bf16 or f32; m, v f32. */
