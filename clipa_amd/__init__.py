@@ -5,7 +5,8 @@ create_model, create_model_and_transforms, create_loss, CLIP, ClipLoss, DistillC
 convert_weights_to_lp,
 get_cast_dtype, list_models, add_model_config; and the trainer's validation (training/train.py: evaluate,
 get_clip_metrics), multi-caption image-text retrieval (`image_text_retrieval`, `evaluate_retrieval`) and the few-shot
-linear probe (`fewshot_lsr`, `fewshot_metrics`, `evaluate_fewshot`).
+linear probe (`fewshot_lsr`, `fewshot_metrics`, `evaluate_fewshot`) and fused fp32 zero-shot classification
+(`build_classifier`, `class_mean_embeddings`, `zero_shot_ranks`, `zero_shot_counts`, `zero_shot_metrics`, `evaluate_zero_shot`).
 """
 from .configs import add_model_config, get_model_config, list_models
 from .factory import (create_loss, create_model, create_model_and_transforms, get_cast_dtype, load_checkpoint)
@@ -20,5 +21,8 @@ from .fewshot import evaluate_fewshot, fewshot_lsr, fewshot_metrics
 from .retrieval_eval import evaluate_retrieval, image_text_retrieval
 from .transform import AugmentationCfg, image_transform
 from .zero import ShardedAdamW
+from . import zero_shot
+from .zero_shot import (build_classifier, class_mean_embeddings, evaluate_zero_shot, zero_shot_counts, zero_shot_metrics,
+                        zero_shot_ranks)
 
 __version__ = "0.4.0"

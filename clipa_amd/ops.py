@@ -1272,6 +1272,68 @@ def fewshot_predict(z, w):
     return out_p[:Nt], out_b[:Nt]
 
 
+def zeroshot_class_mean(emb, offsets, eps=0.0):
+    """The prompt-ensemble classifier of zero-shot classification (zero_shot.py:37-38; _average_embeddings of
+    discriminative_classifier.py:165-170): emb f32 [N, E] with its rows sorted by class, offsets the C + 1 segment bounds (host
+    sequence or tensor: 0 = offsets[0] < ... < offsets[C] = N).  -> W, the [C, E] view of a [C, E rounded up to 4] buffer whose
+    other columns are 0: W_c = m_c / (eps + ||m_c||), m_c the mean of class c's rows, in the fixed order of csrc/zeroshot.hip.
+    An empty class raises ("Classes without embeddings")."""
+    _chk(emb, f32, "emb", 2)
+    emb, lde = _rowmajor(emb)
+    if emb.data_ptr() % 16:
+        emb = emb.clone(memory_format=torch.contiguous_format)
+        lde = emb.shape[1]
+    N, E = emb.shape
+    off = [int(v) for v in (offsets.reshape(-1).tolist() if torch.is_tensor(offsets) else offsets)]
+    if len(off) < 1 or off[0] != 0 or off[-1] != N or any(b < a for a, b in zip(off, off[1:])):
+        raise RuntimeError(f"zeroshot_class_mean: offsets must rise from 0 to N = {N}; got {off[:4]}...{off[-2:]}")
+    empty = [c for c, (a, b) in enumerate(zip(off, off[1:])) if a == b]
+    if empty:
+        raise RuntimeError(f"zeroshot_class_mean: Classes without embeddings: {empty[:8]}{'...' if len(empty) > 8 else ''}")
+    if not float(eps) >= 0.0:
+        raise RuntimeError(f"zeroshot_class_mean: eps = {eps} must be >= 0")
+    C = len(off) - 1
+    ldw = (E + 3) // 4 * 4
+    W = torch.empty((C, ldw), device=emb.device, dtype=f32)
+    if C:
+        offs = torch.tensor(off, dtype=torch.int32).to(emb.device)
+        with _Timed("zeroshot_class_mean", 0.0, 4.0 * (N * E + 3 * C * E)):
+            lib.call("clipa_zeroshot_class_mean", _p(emb), _p(offs), N, C, E, lde, float(eps), _p(W), ldw, _stream())
+    return W[:, :E]
+
+
+def zeroshot_ranks(feat, w, labels):
+    """Rank of every image's best label among the classes, without the [B, C] logits (zero_shot.py:47-50, 77-80;
+    discriminative_classifier.py:303-309): feat f32 [B, E], w f32 [C, E] (class-major classifier), labels int32 [B, Lmax] on the
+    device, 1 <= Lmax <= 32, -1 = no label, other values in [0, C) (the caller's to check: a value outside names no class).
+    v = feat @ w^T in fp32, no scale.  -> int32 [B] (gt, eq, pred): the classes that beat / tie (not themselves labels) the
+    image's best label, and the lowest class index among the row's maxima.  A row without labels: gt = C, eq = 0."""
+    _chk(feat, f32, "feat", 2)
+    _chk(w, f32, "w", 2)
+    _chk(labels, torch.int32, "labels", 2)
+    B, E = feat.shape
+    C, Lmax = w.shape[0], labels.shape[1]
+    if w.shape[1] != E or labels.shape[0] != B:
+        raise RuntimeError(f"zeroshot_ranks: feat {tuple(feat.shape)}, w {tuple(w.shape)} and labels {tuple(labels.shape)} must be "
+                           f"[B, E], [C, E] and [B, Lmax]")
+    if not 1 <= Lmax <= 32:
+        raise RuntimeError(f"zeroshot_ranks: Lmax = {Lmax} labels per image; the kernel takes 1 to 32")
+    out = torch.empty((3, (B + 3) // 4 * 4), device=feat.device, dtype=torch.int32)       # rows 16-byte aligned
+    if B == 0:
+        return tuple(out[k, :0] for k in range(3))
+    if C < 1 or E < 1:
+        raise RuntimeError(f"zeroshot_ranks: C = {C} classes of E = {E} columns: nothing to rank {B} rows against")
+    feat, lda = _aligned_rows(feat)
+    w, ldw = _aligned_rows(w)
+    labels = labels.contiguous()
+    if labels.data_ptr() % 16:
+        labels = labels.clone()
+    with _Timed("zeroshot_ranks", 4.0 * B * C * E):
+        lib.call("clipa_zeroshot_ranks", _p(feat), _p(w), _p(labels), B, C, E, Lmax, lda, ldw, *(_p(out[k]) for k in range(3)),
+                 _stream())
+    return tuple(out[k, :B] for k in range(3))
+
+
 def sum_scale(x, scale, out=None, accumulate=False):
     x = x.contiguous()
     if out is None:

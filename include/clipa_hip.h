@@ -382,6 +382,28 @@ int clipa_fewshot_class_sums(const float* Z, const int32_t* offsets, int64_t N, 
  * pred[n] = the lowest class index among the maxima of row n, best[n] = that logit (finite logits assumed). */
 int clipa_fewshot_predict(const float* Z, const float* W, int64_t Nt, int64_t C, int64_t dim, int64_t ldz, int64_t ldw,
                           int32_t* pred, float* best, void* stream);
+/* Zero-shot classification (clipa_torch/training/zero_shot.py:29-90; clipa_jax/evaluators/proj/image_text/
+ * discriminative_classifier.py:152-171, 302-312).  Everything fp32, every reduction in a fixed order (no float atomics, results
+ * bit-reproducible); pointers 16-byte aligned, matrices row-major.
+ * class mean (zero_shot.py:37-38; _average_embeddings, discriminative_classifier.py:165-170): the rows of emb [N, lde] sorted by
+ * class, offsets int32 [C + 1] in DEVICE memory (class c = rows [offsets[c], offsets[c + 1]), clamped to [0, N]); W [C, ldw],
+ * W_c = m_c / (eps + ||m_c||) with m_c the mean of the rows of class c, columns [E, ldw) = 0; lde, ldw >= E.  eps = 0 is the
+ * torch reference (inputs already unit-norm), eps = 1e-8 the JAX one.  One accumulator per (class, column) in ascending row
+ * order, true division and square root; the order of the sum of squares is in csrc/zeroshot.hip.  An empty class has no mean
+ * ("Classes without embeddings", :164): N < C is CLIPA_ERR_ARG, and a caller checks its offsets before the call - the row of
+ * an empty class comes out NaN.  C = 0 returns CLIPA_OK without a launch. */
+int clipa_zeroshot_class_mean(const float* emb, const int32_t* offsets, int64_t N, int64_t C, int64_t E, int64_t lde, float eps,
+                              float* W, int64_t ldw, void* stream);
+/* ranks (replaces logits = 100 * f @ classifier and accuracy's topk, zero_shot.py:47-50, 77-80, and best_txt / matching of
+ * discriminative_classifier.py:303-309) without the [B, C] logits: A [B, lda] image features, W [C, ldw] classifier (lda,
+ * ldw >= E, multiples of 4), labels int32 [B, Lmax] (1 <= Lmax <= 32, -1 = no label; a value outside [0, C) names no class).
+ * v_ic = A_i . W_c by the arithmetic of clipa_retrieval_ranks (one ascending-k fp32 chain, no scale: the reference's 100 *
+ * changes no order but can merge neighbours).  t_i = max over i's labels of v_ic;
+ * gt[i] = #{c : v_ic > t_i}, eq[i] = #{c not a label of i : v_ic == t_i}, pred[i] = the lowest class index among the maxima of
+ * row i.  A row without labels gets gt = C, eq = 0.  Finite inputs assumed.  O(B + C E) memory, no workspace, plain stores.
+ * B = 0 returns CLIPA_OK without a launch; B > 0 with C = 0 or E = 0 is CLIPA_ERR_ARG, and so is C >= 2^20. */
+int clipa_zeroshot_ranks(const float* A, const float* W, const int32_t* labels, int64_t B, int64_t C, int64_t E, int64_t Lmax,
+                         int64_t lda, int64_t ldw, int32_t* gt, int32_t* eq, int32_t* pred, void* stream);
 
 /* AdamW over one flat tensor (training/main.py:318-326 torch.optim.AdamW + train.py:285-286 clamp is
  * done by the caller): p -= lr*(m_hat/(sqrt(v_hat)+eps) + wd*p). param/grad bf16 or f32; m, v f32. */
