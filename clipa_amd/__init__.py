@@ -6,7 +6,9 @@ convert_weights_to_lp,
 get_cast_dtype, list_models, add_model_config; and the trainer's validation (training/train.py: evaluate,
 get_clip_metrics), multi-caption image-text retrieval (`image_text_retrieval`, `evaluate_retrieval`) and the few-shot
 linear probe (`fewshot_lsr`, `fewshot_metrics`, `evaluate_fewshot`) and fused fp32 zero-shot classification
-(`build_classifier`, `class_mean_embeddings`, `zero_shot_ranks`, `zero_shot_counts`, `zero_shot_metrics`, `evaluate_zero_shot`).
+(`build_classifier`, `class_mean_embeddings`, `zero_shot_ranks`, `zero_shot_counts`, `zero_shot_metrics`, `evaluate_zero_shot`)
+and top-k similarity search (`topk_similarity`, `classify_topk`, `zero_shot_predict`, `retrieve_topk`, `knn_classify`,
+`knn_metrics`).
 """
 from .configs import add_model_config, get_model_config, list_models
 from .factory import (create_loss, create_model, create_model_and_transforms, get_cast_dtype, load_checkpoint)
@@ -24,5 +26,7 @@ from .zero import ShardedAdamW
 from . import zero_shot
 from .zero_shot import (build_classifier, class_mean_embeddings, evaluate_zero_shot, zero_shot_counts, zero_shot_metrics,
                         zero_shot_ranks)
+from . import search
+from .search import classify_topk, knn_classify, knn_metrics, retrieve_topk, topk_similarity, zero_shot_predict
 
 __version__ = "0.4.0"

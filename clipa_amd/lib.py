@@ -98,6 +98,8 @@ SIGNATURES = {
     "clipa_fewshot_predict": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P]),
     "clipa_zeroshot_class_mean": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _F, _P, _I64, _P]),
     "clipa_zeroshot_ranks": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "clipa_topk_workspace": (_I64, [_I64, _I64, _I64, _I64]),
+    "clipa_topk": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _I64, _P]),
     "clipa_adamw": (_I32, [_P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _F, _F, _F, _I64, _F, _P]),
     "clipa_adamw_multi": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _F, _F, _F, _F, _F, _I64, _F, _P, _I32, _F, _F, _P]),
     "clipa_grad_sqnorm_multi": (_I32, [_P, _P, _I32, _I32, _P, _P, _I64, _P]),

@@ -1334,6 +1334,49 @@ def zeroshot_ranks(feat, w, labels):
     return tuple(out[k, :B] for k in range(3))
 
 
+def topk_similarity(q, g, k, scale=None, index_base=0, carry=None, splits=0):
+    """The k best gallery rows of every query without the [Nq, Ng] similarities (zero_shot.py:47-50 `output.topk`;
+    image_text_retrieval.py:77-82): q f32 [Nq, E], g f32 [Ng, E], v = s * q @ g^T in fp32 with s = scale[0] read on the device
+    (None = 1).  -> (values f32 [Nq, k], indices int64 [Nq, k]), best first under the strict order of csrc/topk.hip: the larger
+    value first, equal values (IEEE ==) by the lower index, a NaN before every number; index = index_base + gallery row; with
+    fewer than k entries the tail is (-inf, -1).  carry = (values, indices) of earlier calls over other shards of the gallery
+    (same k): the result is the first k of both.  splits: column splits of the launch, 0 = the entry point's choice; every value
+    in [1, gallery tiles of 128] gives the same output."""
+    _chk(q, f32, "q", 2)
+    _chk(g, f32, "g", 2)
+    Nq, E = q.shape
+    Ng = g.shape[0]
+    k, index_base, splits = int(k), int(index_base), int(splits)
+    if g.shape[1] != E:
+        raise RuntimeError(f"topk_similarity: q {tuple(q.shape)} and g {tuple(g.shape)} must be [Nq, E] and [Ng, E]")
+    if not 1 <= k <= 32:
+        raise RuntimeError(f"topk_similarity: k = {k}; the kernel takes 1 to 32")
+    cv = ci = None
+    if carry is not None:
+        cv, ci = carry
+        _chk(cv, f32, "carry values", 2)
+        _chk(ci, torch.int64, "carry indices", 2)
+        if tuple(cv.shape) != (Nq, k) or tuple(ci.shape) != (Nq, k):
+            raise RuntimeError(f"topk_similarity: carry {tuple(cv.shape)}, {tuple(ci.shape)} must both be [Nq, k] = [{Nq}, {k}]")
+        cv, ci = cv.contiguous(), ci.contiguous()
+        if cv.data_ptr() % 16:
+            cv = cv.clone()
+        if ci.data_ptr() % 16:
+            ci = ci.clone()
+    out_v = torch.empty((Nq, k), device=q.device, dtype=f32)
+    out_i = torch.empty((Nq, k), device=q.device, dtype=torch.int64)
+    if Nq == 0:
+        return out_v, out_i
+    q, ldq = _aligned_rows(q)
+    g, ldg = _aligned_rows(g)
+    scale = _scalar1(scale)
+    ws, wsb = _workspace("clipa_topk_workspace", Nq, Ng, k, splits, device=q.device, floor=16)
+    with _Timed("topk_similarity", 2.0 * Nq * Ng * E):
+        lib.call("clipa_topk", _p(q), _p(g), Nq, Ng, E, ldq, ldg, _p(scale), k, index_base, splits, _p(cv), _p(ci), _p(out_v),
+                 _p(out_i), _p(ws), wsb, _stream())
+    return out_v, out_i
+
+
 def sum_scale(x, scale, out=None, accumulate=False):
     x = x.contiguous()
     if out is None:

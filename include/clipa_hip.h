@@ -404,6 +404,34 @@ int clipa_zeroshot_class_mean(const float* emb, const int32_t* offsets, int64_t 
  * B = 0 returns CLIPA_OK without a launch; B > 0 with C = 0 or E = 0 is CLIPA_ERR_ARG, and so is C >= 2^20. */
 int clipa_zeroshot_ranks(const float* A, const float* W, const int32_t* labels, int64_t B, int64_t C, int64_t E, int64_t Lmax,
                          int64_t lda, int64_t ldw, int32_t* gt, int32_t* eq, int32_t* pred, void* stream);
+/* Top-k similarity search (the `output.topk` of clipa_torch/training/zero_shot.py:47-50 and the top-k lists of
+ * clipa_jax/evaluators/proj/image_text/image_text_retrieval.py:77-82) without the [Nq, Ng] matrix: Q [Nq, ldq] queries, G
+ * [Ng, ldg] gallery rows (ldq, ldg >= E, multiples of 4), v_ij = fl(s * Q_i . G_j) by the arithmetic of clipa_retrieval_ranks
+ * (one ascending-k fp32 chain; s = scale[0] read on the device, NULL = 1).  out_val f32 / out_idx int64 [Nq, k], 1 <= k <= 32:
+ * the first k entries of row i, best first, under the strict total order
+ *   (v, g) precedes (v', g') iff v > v', or v == v' and g < g',       g = index_base + j (0 <= index_base < 2^62).
+ * `==` is IEEE equality: -0 and +0 tie, and a zero is reported as +0.  A NaN precedes every number (torch.topk's convention),
+ * NaNs order among themselves by index and are reported as one quiet NaN: a poisoned row shows it in its first slot.  With
+ * fewer than k entries the tail slots hold value -inf and index -1; they come after every real entry.  The order is strict, so
+ * the result depends on the set of entries alone - not on tiles, splits, timing or shards - and is bit-reproducible; no float
+ * atomics.
+ * Shards: carry_val / carry_idx [Nq, k] (both or neither; same k; index -1 = empty slot, its value ignored) hold the lists of
+ * earlier calls over other, disjoint index ranges; the output is the first k of (carry U this call's entries) and may alias
+ * the carry.  The shards of a gallery in any sequence give bit for bit the lists of one call over the whole gallery.
+ * Launches: the grid is (128-row query tiles) x splits, each split sweeping a contiguous range of the 128-row gallery tiles
+ * into per-row lists in the workspace, then one wave per row merges the splits and the carry.  splits = 0 lets the entry choose
+ * (min(gallery tiles, max(1, 512 / query tiles)): two workgroups for each of 256 CUs); any value in [1, gallery tiles] gives the
+ * same output.  Workspace: clipa_topk_workspace(Nq, Ng, k, splits) bytes = splits * Nq * k * 8 (at least 16), O(Nq k) memory.
+ * Nq == 0 returns CLIPA_OK without a launch.  Ng == 0 or E == 0 with Nq > 0 is valid (Q and G are then not read and may be
+ * NULL): the output is the carry, or empty lists; E == 0 with Ng > 0 makes every value +0, so the indices run from index_base.
+ * CLIPA_ERR_ARG before any launch: k outside [1, 32], negative sizes, Nq or Ng >= 2^31 - 128 (a larger gallery goes through
+ * shards), 128 * ld * 4 >= 2^30, leading dimensions below E or not multiples of 4, null or not 16-byte aligned pointers, one
+ * carry pointer without the other, index_base out of range, splits outside [0, max(1, gallery tiles)], query tiles * splits
+ * >= 2^31, workspace too small. */
+int64_t clipa_topk_workspace(int64_t Nq, int64_t Ng, int64_t k, int64_t splits);
+int clipa_topk(const float* Q, const float* G, int64_t Nq, int64_t Ng, int64_t E, int64_t ldq, int64_t ldg, const float* scale,
+               int64_t k, int64_t index_base, int64_t splits, const float* carry_val, const int64_t* carry_idx, float* out_val,
+               int64_t* out_idx, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* AdamW over one flat tensor (training/main.py:318-326 torch.optim.AdamW + train.py:285-286 clamp is
  * done by the caller): p -= lr*(m_hat/(sqrt(v_hat)+eps) + wd*p). param/grad bf16 or f32; m, v f32. */
