@@ -22,6 +22,15 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 void clipa_set_error(const char* fmt, ...);
 int clipa_check_launch(const char* what);
+// every pointer non-null and 16-byte aligned, or CLIPA_ERR_ARG naming the entry point and the pointer's position in the list
+inline int clipa_check_ptrs16(const char* name, std::initializer_list<const void*> ptrs) {
+  int i = 0;
+  for (const void* p : ptrs) {
+    if (!p || ((uintptr_t)p & 15)) { clipa_set_error("%s: pointer argument %d is null or not 16-byte aligned", name, i); return CLIPA_ERR_ARG; }
+    ++i;
+  }
+  return CLIPA_OK;
+}
 
 // Per-device launch state (host; defined in gemm_nt.hip).
 namespace clipa_gemm {

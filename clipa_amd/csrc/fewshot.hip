@@ -107,29 +107,25 @@ __global__ __launch_bounds__(256) void fewshot_whiten_kernel(const float* __rest
 __global__ __launch_bounds__(RTHREADS, 2) void fewshot_gram_kernel(const char* __restrict__ A, int M, int E, long lda,
                                                                    float* __restrict__ S, long lds) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int L = lane & 31, hi = lane >> 5;
-  const int wm = wave >> 1, wn = wave & 1;
+  const RankLane t = rank_lane();
   const int T = (M + RT - 1) / RT;
   int tm = 0, b = blockIdx.x;
   while (b >= T - tm) { b -= T - tm; ++tm; }  // row tm of the upper triangle holds T - tm tiles
   const int tn = tm + b;
   const int m0 = tm * RT, n0 = tn * RT;
-  const int rowsA = min(RT, M - m0), rowsB = min(RT, M - n0);
-  const __amdgpu_buffer_rsrc_t rsA = make_rsrc(A + (size_t)m0 * lda * 4, (unsigned)(rowsA * lda * 4));
-  const __amdgpu_buffer_rsrc_t rsB = make_rsrc(A + (size_t)n0 * lda * 4, (unsigned)(rowsB * lda * 4));
+  int rowsA, rowsB;
+  const __amdgpu_buffer_rsrc_t rsA = rank_rows(A, m0, M, lda, &rowsA);
+  const __amdgpu_buffer_rsrc_t rsB = rank_rows(A, n0, M, lda, &rowsB);
   f32x16 acc[2][2];
   rank_tile(smem, rsA, rsB, lda, lda, E, acc);
 #pragma unroll
   for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = m0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+      const int i = t.row(mi * 16 + r, m0);
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
-        const int j = n0 + wn * 64 + ni * 32 + L;
+        const int j = t.col(ni, n0);
         if (i <= j && j < M) {                 // i <= j < M
           const float v = acc[mi][ni][r];
           S[(long)i * lds + j] = v;
@@ -159,101 +155,64 @@ __global__ __launch_bounds__(64) void fewshot_signsum_kernel(int dim, int C, flo
   for (int c = 0; c < C; ++c) row[c] = 2.0f * row[c] - total;
 }
 
+// A row's running best: the logit and its class (NONE: no class seen yet).  fs_better picks by a strict total order on finite
+// logits - the larger value, equal values by the lower class - so the best of a set does not depend on the order of the meeting.
+struct FsBest { float v; int c; };
+__device__ __forceinline__ FsBest lane_xor(FsBest x, int b) { return {__shfl_xor(x.v, b, 64), __shfl_xor(x.c, b, 64)}; }
+__device__ __forceinline__ FsBest fs_better(FsBest a, FsBest o) { return o.v > a.v || (o.v == a.v && o.c < a.c) ? o : a; }
+
 // One workgroup per 128 test rows, over the class tiles in ascending order.  A lane's accumulator columns are classes
-// tn * 128 + wn * 64 + ni * 32 + L: ascending in (tn, ni), so per row "replace only on strictly greater" keeps the lowest class
-// of the lane's maxima.  The 64 candidates of a row (32 lanes of each of the two column waves) meet in LDS once, at the end;
+// tn * 128 + col(ni): ascending in (tn, ni), so per row "replace only on strictly greater" keeps the lowest class of the lane's
+// maxima.  The 64 candidates of a row (32 lanes of each of the two column waves) meet once, at the end (halve32, rank_row_meet);
 // there equal values resolve to the lower class.
 __global__ __launch_bounds__(RTHREADS, 2) void fewshot_predict_kernel(const char* __restrict__ Zs, const char* __restrict__ W,
                                                                       int Nt, int C, int dim, long ldz, long ldw,
                                                                       int* __restrict__ pred, float* __restrict__ best) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int L = lane & 31, hi = lane >> 5;
-  const int wm = wave >> 1, wn = wave & 1;
+  const RankLane t = rank_lane();
   const int m0 = blockIdx.x * RT;
-  const int rowsA = min(RT, Nt - m0);
-  const __amdgpu_buffer_rsrc_t rsA = make_rsrc(Zs + (size_t)m0 * ldz * 4, (unsigned)(rowsA * ldz * 4));
+  int rowsA, rowsB;
+  const __amdgpu_buffer_rsrc_t rsA = rank_rows(Zs, m0, Nt, ldz, &rowsA);
   constexpr int NONE = 0x7fffffff;
-  float bv[32];
-  int bc[32];
+  FsBest best_q[32];
 #pragma unroll
-  for (int q = 0; q < 32; ++q) { bv[q] = -__builtin_huge_valf(); bc[q] = NONE; }
+  for (int q = 0; q < 32; ++q) best_q[q] = {-__builtin_huge_valf(), NONE};
 
   const int Tc = (C + RT - 1) / RT;
   f32x16 acc[2][2];
   for (int tn = 0; tn < Tc; ++tn) {
     const int n0 = tn * RT;
-    const int rowsB = min(RT, C - n0);
-    const __amdgpu_buffer_rsrc_t rsB = make_rsrc(W + (size_t)n0 * ldw * 4, (unsigned)(rowsB * ldw * 4));
+    const __amdgpu_buffer_rsrc_t rsB = rank_rows(W, n0, C, ldw, &rowsB);
     __syncthreads();                          // the previous tile's readers are done with the ring
     rank_tile(smem, rsA, rsB, ldz, ldw, dim, acc);
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) {
-      const int cls = n0 + wn * 64 + ni * 32 + L;
+      const int cls = t.col(ni, n0);
       if (cls < C) {
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float v = acc[mi][ni][r];
-            const bool take = v > bv[mi * 16 + r] || bc[mi * 16 + r] == NONE;
-            bv[mi * 16 + r] = take ? v : bv[mi * 16 + r];
-            bc[mi * 16 + r] = take ? cls : bc[mi * 16 + r];
-          }
+        for (int q = 0; q < 32; ++q) {
+          const float v = acc[q >> 4][ni][q & 15];
+          const bool take = v > best_q[q].v || best_q[q].c == NONE;
+          best_q[q] = take ? FsBest{v, cls} : best_q[q];
+        }
       }
     }
   }
-
-  // per wave a [64 rows][32 lanes] image of values and one of classes (4 x 16 KiB = the ring); slot L of row i sits at column
-  // L ^ (i & 31), so the 32 lanes that write a row and the 32 rows that one read sweeps both hit 32 distinct banks
-  __syncthreads();
-  float* wv = (float*)(smem + wave * 16384);
-  int* wc = (int*)(smem + wave * 16384 + 8192);
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int il = mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-      wv[il * 32 + (L ^ (il & 31))] = bv[mi * 16 + r];
-      wc[il * 32 + (L ^ (il & 31))] = bc[mi * 16 + r];
-    }
-  __syncthreads();
-  float v = wv[lane * 32 + (lane & 31)];       // slot 0 of row `lane` of this wave's 64 rows
-  int c = wc[lane * 32 + (lane & 31)];
-#pragma unroll 4
-  for (int s = 1; s < 32; ++s) {
-    const float ov = wv[lane * 32 + (s ^ (lane & 31))];
-    const int oc = wc[lane * 32 + (s ^ (lane & 31))];
-    const bool take = ov > v || (ov == v && oc < c);
-    v = take ? ov : v;
-    c = take ? oc : c;
-  }
-  __syncthreads();                            // everyone has read: the first 2 KiB now carry the two column waves' results
-  float* fv = (float*)smem;                   // [2 wn][128]
-  int* fc = (int*)(smem + 1024);
-  fv[wn * RT + wm * 64 + lane] = v;
-  fc[wn * RT + wm * 64 + lane] = c;
-  __syncthreads();
-  if (tid < rowsA) {
-    const float v0 = fv[tid], v1 = fv[RT + tid];
-    const int c0 = fc[tid], c1 = fc[RT + tid];
-    const bool take = v1 > v0 || (v1 == v0 && c1 < c0);
-    pred[m0 + tid] = take ? c1 : c0;
-    best[m0 + tid] = take ? v1 : v0;
+  halve32(best_q, t.L, fs_better);
+  __syncthreads();                            // the ring is dead: its first 2 KiB take the two column waves' results
+  const FsBest b = rank_row_meet(t, (FsBest*)smem, best_q[0], fs_better);
+  if (t.tid < rowsA) {
+    pred[m0 + t.tid] = b.c;
+    best[m0 + t.tid] = b.v;
   }
 }
 
 LdsOptIn g_fs_lds;
 
-int fs_ptrs(const char* name, std::initializer_list<const void*> ptrs) {
-  int i = 0;
-  for (const void* p : ptrs) {
-    if (!p || ((uintptr_t)p & 15)) { clipa_set_error("%s: pointer argument %d is null or not 16-byte aligned", name, i); return CLIPA_ERR_ARG; }
-    ++i;
-  }
-  return 0;
+template <class K, class... A>
+int fs_launch(K kernel, int64_t grid, void* stream, const char* name, A... args) {
+  return rank_launch(g_fs_lds, {(const void*)fewshot_gram_kernel, (const void*)fewshot_predict_kernel}, 2 * R_STAGE, "fewshot", kernel,
+                     grid, 2 * R_STAGE, stream, name, args...);
 }
 int fs_rows(const char* name, const void* index, int64_t N, int64_t Ntot, int64_t D, int64_t ldx) {
   if (N < 0 || Ntot < 0 || D < 0 || ldx < D || N >= (1L << 31) || Ntot >= (1L << 31) || D >= (1L << 31) - 64) {
@@ -274,8 +233,8 @@ extern "C" int clipa_fewshot_moments(const float* x, const int32_t* index, int64
                                      float* mean, float* std, void* stream) {
   if (int rc = fs_rows("fewshot_moments", index, N, Ntot, D, ldx)) return rc;
   if (D == 0) return CLIPA_OK;
-  if (int rc = fs_ptrs("fewshot_moments", {mean, std})) return rc;
-  if (N > 0) if (int rc = fs_ptrs("fewshot_moments", {x})) return rc;       // N = 0: x is never read, mean = std = 0 / 0 = NaN
+  if (int rc = clipa_check_ptrs16("fewshot_moments", {mean, std})) return rc;
+  if (N > 0) if (int rc = clipa_check_ptrs16("fewshot_moments", {x})) return rc;       // N = 0: x is never read, mean = std = 0 / 0 = NaN
   hipLaunchKernelGGL(fewshot_moments_kernel, dim3((unsigned)((D + MOM_COLS - 1) / MOM_COLS)), dim3(MOM_COLS * MOM_SLICES), 0,
                      (hipStream_t)stream, x, index, (int)N, (int)Ntot, (int)D, (long)ldx, mean, std);
   return clipa_check_launch("fewshot_moments");
@@ -290,8 +249,8 @@ extern "C" int clipa_fewshot_whiten(const float* x, const int32_t* index, int64_
     return CLIPA_ERR_ARG;
   }
   if (N == 0) return CLIPA_OK;
-  if (int rc = fs_ptrs("fewshot_whiten", {Z})) return rc;
-  if (D > 0) if (int rc = fs_ptrs("fewshot_whiten", {x, mean, std})) return rc;
+  if (int rc = clipa_check_ptrs16("fewshot_whiten", {Z})) return rc;
+  if (D > 0) if (int rc = clipa_check_ptrs16("fewshot_whiten", {x, mean, std})) return rc;
   if (Zt && ((uintptr_t)Zt & 15)) { clipa_set_error("fewshot_whiten: Zt is not 16-byte aligned"); return CLIPA_ERR_ARG; }
   const int64_t rows = Zt && ldt > N ? ldt : N;
   const int64_t gx = (rows + WT - 1) / WT, gy = (ldz + WT - 1) / WT;
@@ -305,19 +264,14 @@ extern "C" int clipa_fewshot_gram(const float* A, int64_t M, int64_t E, int64_t 
   if (M < 0 || E < 0 || lds < M) { clipa_set_error("fewshot_gram: M = %ld, E = %ld, lds = %ld out of range (lds >= M)", (long)M, (long)E, (long)lds); return CLIPA_ERR_ARG; }
   if (M == 0) return CLIPA_OK;
   if (E == 0) {                               // the empty sum: S = 0
-    if (int rc = fs_ptrs("fewshot_gram", {S})) return rc;
+    if (int rc = clipa_check_ptrs16("fewshot_gram", {S})) return rc;
     const hipError_t e = hipMemset2DAsync(S, (size_t)lds * 4, 0, (size_t)M * 4, (size_t)M, (hipStream_t)stream);
     if (e != hipSuccess) { clipa_set_error("fewshot_gram: hipMemset2DAsync: %s", hipGetErrorString(e)); return CLIPA_ERR_LAUNCH; }
     return CLIPA_OK;
   }
   const int64_t T = (M + RT - 1) / RT;
   if (int rc = rank_check_args("fewshot_gram", E, lda, lda, M >= (1L << 30) || T * (T + 1) / 2 >= (1L << 31), "M", {A, S}, nullptr)) return rc;
-  int dev = 0;
-  if (int rc = current_device(&dev)) return rc;
-  if (int rc = g_fs_lds.ensure(dev, {(const void*)fewshot_gram_kernel, (const void*)fewshot_predict_kernel}, 2 * R_STAGE, "fewshot")) return rc;
-  hipLaunchKernelGGL(fewshot_gram_kernel, dim3((unsigned)(T * (T + 1) / 2)), dim3(RTHREADS), 2 * R_STAGE, (hipStream_t)stream,
-                     (const char*)A, (int)M, (int)E, (long)lda, S, (long)lds);
-  return clipa_check_launch("fewshot_gram");
+  return fs_launch(fewshot_gram_kernel, T * (T + 1) / 2, stream, "fewshot_gram", (const char*)A, (int)M, (int)E, (long)lda, S, (long)lds);
 }
 
 extern "C" int clipa_fewshot_class_sums(const float* Z, const int32_t* offsets, int64_t N, int64_t dim, int64_t C, int64_t ldz,
@@ -328,8 +282,8 @@ extern "C" int clipa_fewshot_class_sums(const float* Z, const int32_t* offsets, 
     return CLIPA_ERR_ARG;
   }
   if (dim == 0 || C == 0) return CLIPA_OK;
-  if (int rc = fs_ptrs("fewshot_class_sums", {offsets, R})) return rc;
-  if (N > 0) if (int rc = fs_ptrs("fewshot_class_sums", {Z})) return rc;
+  if (int rc = clipa_check_ptrs16("fewshot_class_sums", {offsets, R})) return rc;
+  if (N > 0) if (int rc = clipa_check_ptrs16("fewshot_class_sums", {Z})) return rc;
   const unsigned gx = (unsigned)((dim + 63) / 64);
   hipLaunchKernelGGL(fewshot_segsum_kernel, dim3(gx, (unsigned)C), dim3(64), 0, (hipStream_t)stream, Z, offsets, (int)N, (int)dim,
                      (long)ldz, R, (long)ldr);
@@ -344,17 +298,13 @@ extern "C" int clipa_fewshot_predict(const float* Z, const float* W, int64_t Nt,
   if (Nt == 0) return CLIPA_OK;
   if (C == 0) { clipa_set_error("fewshot_predict: C = 0 classes for Nt = %ld rows (an argmax over nothing)", (long)Nt); return CLIPA_ERR_ARG; }
   if (dim == 0) {                             // every logit is the empty sum 0: class 0 wins with 0
-    if (int rc = fs_ptrs("fewshot_predict", {pred, best})) return rc;
+    if (int rc = clipa_check_ptrs16("fewshot_predict", {pred, best})) return rc;
     hipError_t e = hipMemsetAsync(pred, 0, (size_t)Nt * 4, (hipStream_t)stream);
     if (e == hipSuccess) e = hipMemsetAsync(best, 0, (size_t)Nt * 4, (hipStream_t)stream);
     if (e != hipSuccess) { clipa_set_error("fewshot_predict: hipMemsetAsync: %s", hipGetErrorString(e)); return CLIPA_ERR_LAUNCH; }
     return CLIPA_OK;
   }
   if (int rc = rank_check_args("fewshot_predict", dim, ldz, ldw, Nt >= (1L << 31) - RT || C >= (1L << 31) - RT, "Nt, C", {Z, W, pred, best}, nullptr)) return rc;
-  int dev = 0;
-  if (int rc = current_device(&dev)) return rc;
-  if (int rc = g_fs_lds.ensure(dev, {(const void*)fewshot_gram_kernel, (const void*)fewshot_predict_kernel}, 2 * R_STAGE, "fewshot")) return rc;
-  hipLaunchKernelGGL(fewshot_predict_kernel, dim3((unsigned)((Nt + RT - 1) / RT)), dim3(RTHREADS), 2 * R_STAGE, (hipStream_t)stream,
-                     (const char*)Z, (const char*)W, (int)Nt, (int)C, (int)dim, (long)ldz, (long)ldw, pred, best);
-  return clipa_check_launch("fewshot_predict");
+  return fs_launch(fewshot_predict_kernel, (Nt + RT - 1) / RT, stream, "fewshot_predict", (const char*)Z, (const char*)W, (int)Nt,
+                   (int)C, (int)dim, (long)ldz, (long)ldw, pred, best);
 }

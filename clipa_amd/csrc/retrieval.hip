@@ -30,11 +30,8 @@ struct RankArgs {
 template <bool DIAG>
 __global__ __launch_bounds__(RTHREADS, 2) void retrieval_kernel(RankArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int L = lane & 31, hi = lane >> 5;
-  const int wm = wave >> 1, wn = wave & 1;   // wave tile: 64 (i) x 64 (j)
+  const RankLane t = rank_lane();
+  const int tid = t.tid;
   const int T = (p.N + RT - 1) / RT;
   int tm, tn;
   if (DIAG) {
@@ -44,9 +41,9 @@ __global__ __launch_bounds__(RTHREADS, 2) void retrieval_kernel(RankArgs p) {
     tn = blockIdx.x - tm * T;
   }
   const int m0 = tm * RT, n0 = tn * RT;
-  const int rowsA = min(RT, p.N - m0), rowsB = min(RT, p.N - n0);
-  const __amdgpu_buffer_rsrc_t rsA = make_rsrc(p.A + (size_t)m0 * p.lda * 4, (unsigned)(rowsA * p.lda * 4));
-  const __amdgpu_buffer_rsrc_t rsB = make_rsrc(p.B + (size_t)n0 * p.ldb * 4, (unsigned)(rowsB * p.ldb * 4));
+  int rowsA, rowsB;
+  const __amdgpu_buffer_rsrc_t rsA = rank_rows(p.A, m0, p.N, p.lda, &rowsA);
+  const __amdgpu_buffer_rsrc_t rsB = rank_rows(p.B, n0, p.N, p.ldb, &rowsB);
 
   // the positives of this tile's rows (tid < 128) and columns: loaded now, used in the epilogue
   float dpos = 0.f;
@@ -58,28 +55,26 @@ __global__ __launch_bounds__(RTHREADS, 2) void retrieval_kernel(RankArgs p) {
   f32x16 acc[2][2];
   rank_tile(smem, rsA, rsB, p.lda, p.ldb, p.E, acc);
 
-  // D fragment: lane holds column j = n0 + wn*64 + ni*32 + L and rows i = m0 + wm*64 + mi*32 + (r&3) + 8*(r>>2) + 4*hi
   const float s = p.scale ? p.scale[0] : 1.0f;
   if (DIAG) {
     // zero the counts of this tile's rows, write v_ii
     if (tid < RT && m0 + tid < p.N) {
       p.i2t_gt[m0 + tid] = 0; p.i2t_eq[m0 + tid] = 0; p.t2i_gt[m0 + tid] = 0; p.t2i_eq[m0 + tid] = 0;
     }
-    if (wm == wn) {
+    if (t.wm == t.wn) {                       // the waves that hold the tile's diagonal: in acc[mi][mi], where row == column
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int il = mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          const int i = m0 + wm * 64 + il;
-          if (il == mi * 32 + L && i < p.N) p.diag[i] = s * acc[mi][mi][r];
+          const int il = t.row(mi * 16 + r);
+          if (il == t.col(mi) && m0 + il < p.N) p.diag[m0 + il] = s * acc[mi][mi][r];
         }
     }
     return;
   }
 
   // the positive of column j is row j: the identity correspondence of retrieval_multi.hip
-  const int cj[2] = {n0 + wn * 64 + L, n0 + wn * 64 + 32 + L};
+  const int cj[2] = {t.col(0, n0), t.col(1, n0)};
   rank_count(smem, m0, n0, rowsA, rowsB, dpos, s, cj, acc, p.i2t_gt, p.i2t_eq, p.t2i_gt, p.t2i_eq);
 }
 
@@ -101,16 +96,14 @@ extern "C" int clipa_retrieval_ranks(const float* A, const float* B, int64_t N, 
   if (int rc = rank_check_args("retrieval_ranks", E, lda, ldb, N >= (1L << 30), "N",
                                {A, B, i2t_gt, i2t_eq, t2i_gt, t2i_eq, workspace}, scale)) return rc;
   if (workspace_bytes < clipa_retrieval_ranks_workspace(N)) { clipa_set_error("retrieval_ranks: workspace too small"); return CLIPA_ERR_ARG; }
-  int dev = 0;
-  if (int rc = current_device(&dev)) return rc;
-  if (int rc = g_rk_lds.ensure(dev, {(const void*)retrieval_kernel<true>, (const void*)retrieval_kernel<false>}, 2 * R_STAGE, "retrieval")) return rc;
   const int64_t T = (N + RT - 1) / RT;
   RankArgs a = {};
   a.A = (const char*)A; a.B = (const char*)B; a.N = (int)N; a.E = (int)E; a.lda = lda; a.ldb = ldb; a.scale = scale;
   a.diag = (float*)workspace; a.i2t_gt = i2t_gt; a.i2t_eq = i2t_eq; a.t2i_gt = t2i_gt; a.t2i_eq = t2i_eq;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(retrieval_kernel<true>, dim3((unsigned)T), dim3(RTHREADS), 2 * R_STAGE, st, a);
-  if (int rc = clipa_check_launch("retrieval_diag")) return rc;
-  hipLaunchKernelGGL(retrieval_kernel<false>, dim3((unsigned)(T * T)), dim3(RTHREADS), 2 * R_STAGE, st, a);
-  return clipa_check_launch("retrieval_ranks");
+  auto launch = [&](auto kernel, int64_t grid, const char* name) {
+    return rank_launch(g_rk_lds, {(const void*)retrieval_kernel<true>, (const void*)retrieval_kernel<false>}, 2 * R_STAGE,
+                       "retrieval", kernel, grid, 2 * R_STAGE, stream, name, a);
+  };
+  if (int rc = launch(retrieval_kernel<true>, T, "retrieval_diag")) return rc;
+  return launch(retrieval_kernel<false>, T * T, "retrieval_ranks");
 }

@@ -32,40 +32,29 @@ struct MultiArgs {
   int* i2t_gt; int* i2t_eq; int* t2i_gt; int* t2i_eq;
 };
 
-// order-preserving map float -> unsigned (a < b  <=>  key(a) < key(b) for non-NaN a, b; -0 < +0) and its inverse
-__device__ __forceinline__ unsigned fkey(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : u | 0x80000000u;
-}
-__device__ __forceinline__ float fdekey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? k & 0x7fffffffu : ~k); }
-
 __global__ __launch_bounds__(RTHREADS) void multi_init_kernel(MultiArgs p) {
   const int g = blockIdx.x * RTHREADS + threadIdx.x;
-  if (g < p.Ni) { p.mkey[g] = fkey(-__builtin_huge_valf()); p.i2t_gt[g] = 0; p.i2t_eq[g] = 0; }
+  if (g < p.Ni) { p.mkey[g] = f32_key(-__builtin_huge_valf()); p.i2t_gt[g] = 0; p.i2t_eq[g] = 0; }
   if (g < p.Nt) { p.pos[g] = __builtin_nanf(""); p.t2i_gt[g] = 0; p.t2i_eq[g] = 0; }
 }
 
 template <bool POS>
 __global__ __launch_bounds__(RTHREADS, 2) void retrieval_multi_kernel(MultiArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int L = lane & 31, hi = lane >> 5;
-  const int wm = wave >> 1, wn = wave & 1;
+  const RankLane t = rank_lane();
+  const int tid = t.tid;
   const int Tt = (p.Nt + RT - 1) / RT;
   const int tm0 = POS ? 0 : blockIdx.x / Tt;
   const int tn = POS ? blockIdx.x : blockIdx.x - tm0 * Tt;
   const int n0 = tn * RT;
-  const int rowsB = min(RT, p.Nt - n0);
-  const __amdgpu_buffer_rsrc_t rsB = make_rsrc(p.B + (size_t)n0 * p.ldb * 4, (unsigned)(rowsB * p.ldb * 4));
+  int rowsA, rowsB;
+  const __amdgpu_buffer_rsrc_t rsB = rank_rows(p.B, n0, p.Nt, p.ldb, &rowsB);
   const float s = p.scale ? p.scale[0] : 1.0f;
   // c of this lane's two accumulator columns (-1 past Nt); only ever compared, never used as an index
   int cj[2];
 #pragma unroll
   for (int ni = 0; ni < 2; ++ni) {
-    const int jl = wn * 64 + ni * 32 + L;
-    cj[ni] = jl < rowsB ? p.c[n0 + jl] : -1;
+    cj[ni] = t.col(ni) < rowsB ? p.c[t.col(ni, n0)] : -1;
   }
   f32x16 acc[2][2];
 
@@ -83,20 +72,19 @@ __global__ __launch_bounds__(RTHREADS, 2) void retrieval_multi_kernel(MultiArgs 
       // doubles as the barrier before the ring is staged again
       if (!__syncthreads_or(valid && ct / RT == tm)) continue;
       const int m0 = tm * RT;
-      const int rowsA = min(RT, p.Ni - m0);
-      const __amdgpu_buffer_rsrc_t rsA = make_rsrc(p.A + (size_t)m0 * p.lda * 4, (unsigned)(rowsA * p.lda * 4));
+      const __amdgpu_buffer_rsrc_t rsA = rank_rows(p.A, m0, p.Ni, p.lda, &rowsA);
       rank_tile(smem, rsA, rsB, p.lda, p.ldb, p.E, acc);
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int i = m0 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+          const int i = t.row(mi * 16 + r, m0);
 #pragma unroll
           for (int ni = 0; ni < 2; ++ni)
             if (cj[ni] == i && i < p.Ni) {      // rows past Ni: a bad c must not reach them
               const float v = s * acc[mi][ni][r];
-              p.pos[n0 + wn * 64 + ni * 32 + L] = v;
-              atomicMax(p.mkey + i, fkey(v));
+              p.pos[t.col(ni, n0)] = v;
+              atomicMax(p.mkey + i, f32_key(v));
             }
         }
     }
@@ -104,12 +92,11 @@ __global__ __launch_bounds__(RTHREADS, 2) void retrieval_multi_kernel(MultiArgs 
   }
 
   const int m0 = tm0 * RT;
-  const int rowsA = min(RT, p.Ni - m0);
-  const __amdgpu_buffer_rsrc_t rsA = make_rsrc(p.A + (size_t)m0 * p.lda * 4, (unsigned)(rowsA * p.lda * 4));
+  const __amdgpu_buffer_rsrc_t rsA = rank_rows(p.A, m0, p.Ni, p.lda, &rowsA);
   // the positives of this tile's rows (tid < 128: m_i) and columns (p_t): loaded now, used in the epilogue
   float dpos = 0.f;
   if (tid < RT) {
-    if (tid < rowsA) dpos = fdekey(p.mkey[m0 + tid]);
+    if (tid < rowsA) dpos = f32_unkey(p.mkey[m0 + tid]);
   } else if (tid - RT < rowsB) {
     dpos = p.pos[n0 + tid - RT];
   }
@@ -143,9 +130,6 @@ extern "C" int clipa_retrieval_ranks_multi(const float* A, const float* B, const
   if (int rc = rank_check_args("retrieval_ranks_multi", E, lda, ldb, Ni >= (1L << 30) || Nt >= (1L << 30) || Ti * Tt >= (1L << 31),
                                "Ni, Nt", {A, B, txt2img, i2t_gt, i2t_eq, t2i_gt, t2i_eq, workspace}, scale)) return rc;
   if (workspace_bytes < clipa_retrieval_ranks_multi_workspace(Ni, Nt)) { clipa_set_error("retrieval_ranks_multi: workspace too small"); return CLIPA_ERR_ARG; }
-  int dev = 0;
-  if (int rc = current_device(&dev)) return rc;
-  if (int rc = g_rkm_lds.ensure(dev, {(const void*)retrieval_multi_kernel<true>, (const void*)retrieval_multi_kernel<false>}, 2 * R_STAGE, "retrieval_multi")) return rc;
   MultiArgs a = {};
   a.A = (const char*)A; a.B = (const char*)B; a.c = txt2img; a.Ni = (int)Ni; a.Nt = (int)Nt; a.E = (int)E;
   a.lda = lda; a.ldb = ldb; a.scale = scale;
@@ -155,8 +139,10 @@ extern "C" int clipa_retrieval_ranks_multi(const float* A, const float* B, const
   const int64_t nmax = Ni > Nt ? Ni : Nt;
   hipLaunchKernelGGL(multi_init_kernel, dim3((unsigned)((nmax + RTHREADS - 1) / RTHREADS)), dim3(RTHREADS), 0, st, a);
   if (int rc = clipa_check_launch("retrieval_multi_init")) return rc;
-  hipLaunchKernelGGL(retrieval_multi_kernel<true>, dim3((unsigned)Tt), dim3(RTHREADS), 2 * R_STAGE, st, a);
-  if (int rc = clipa_check_launch("retrieval_multi_positives")) return rc;
-  hipLaunchKernelGGL(retrieval_multi_kernel<false>, dim3((unsigned)(Ti * Tt)), dim3(RTHREADS), 2 * R_STAGE, st, a);
-  return clipa_check_launch("retrieval_ranks_multi");
+  auto launch = [&](auto kernel, int64_t grid, const char* name) {
+    return rank_launch(g_rkm_lds, {(const void*)retrieval_multi_kernel<true>, (const void*)retrieval_multi_kernel<false>},
+                       2 * R_STAGE, "retrieval_multi", kernel, grid, 2 * R_STAGE, stream, name, a);
+  };
+  if (int rc = launch(retrieval_multi_kernel<true>, Tt, "retrieval_multi_positives")) return rc;
+  return launch(retrieval_multi_kernel<false>, Ti * Tt, "retrieval_ranks_multi");
 }

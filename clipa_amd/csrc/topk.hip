@@ -41,13 +41,9 @@ constexpr int TK_RING = 2 * R_STAGE;          // the 64 KiB of rank_tile, then o
 
 __device__ __forceinline__ unsigned tk_ord(float v) {
   if (v != v) return 0xffffffffu;
-  if (v == 0.f) v = 0.f;                      // -0 -> +0
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return f32_key(v == 0.f ? 0.f : v);         // -0 -> +0
 }
-__device__ __forceinline__ float tk_unord(unsigned o) {   // 0xffffffff -> 0x7fffffff, a NaN
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
+__device__ __forceinline__ float tk_unord(unsigned o) { return f32_unkey(o); }   // 0xffffffff -> 0x7fffffff, a NaN
 
 // maximum over the 64 lanes, returned uniform.  Inclusive scan within each row of 16 lanes (row_shr 1, 2, 4, 8; a lane without
 // a source takes 0, the identity), then row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3: lane 63 holds it.
@@ -68,27 +64,23 @@ __global__ __launch_bounds__(RTHREADS, 2) void topk_tile_kernel(const char* __re
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* val = (float*)smem;                                              // [128][128] after rank_tile
   unsigned long long* lst = (unsigned long long*)(smem + TK_RING);        // [128][k], sorted, 0 = empty
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int L = lane & 31, hi = lane >> 5;
-  const int wm = wave >> 1, wn = wave & 1;
+  const RankLane t = rank_lane();
+  const int tid = t.tid, lane = t.lane, wave = t.wave;
   const int tq = blockIdx.x / splits, sp = blockIdx.x - tq * splits;
   const int m0 = tq * RT;
-  const int rowsA = min(RT, Nq - m0);
+  int rowsA, rowsB;
   const int Tg = (Ng + RT - 1) / RT;
   const int t_lo = (int)((long)sp * Tg / splits), t_hi = (int)((long)(sp + 1) * Tg / splits);
-  const __amdgpu_buffer_rsrc_t rsA = make_rsrc(Q + (size_t)m0 * ldq * 4, (unsigned)(rowsA * ldq * 4));
+  const __amdgpu_buffer_rsrc_t rsA = rank_rows(Q, m0, Nq, ldq, &rowsA);
   const float s = scale ? scale[0] : 1.0f;
 
   for (int i = tid; i < RT * k; i += RTHREADS) lst[i] = 0ull;             // published by the first barrier of the sweep
   f32x16 acc[2][2];
   for (int tn = t_lo; tn < t_hi; ++tn) {
     const int n0 = tn * RT;
-    const int rowsB = min(RT, Ng - n0);
+    const __amdgpu_buffer_rsrc_t rsB = rank_rows(G, n0, Ng, ldg, &rowsB);
     __syncthreads();                          // the previous tile's readers are done with the ring
     if (E > 0) {
-      const __amdgpu_buffer_rsrc_t rsB = make_rsrc(G + (size_t)n0 * ldg * 4, (unsigned)(rowsB * ldg * 4));
       rank_tile(smem, rsA, rsB, ldq, ldg, E, acc);
     } else {
 #pragma unroll
@@ -105,7 +97,7 @@ __global__ __launch_bounds__(RTHREADS, 2) void topk_tile_kernel(const char* __re
       for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          val[(wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi) * RT + wn * 64 + ni * 32 + L] = s * acc[mi][ni][r];
+          val[t.row(mi * 16 + r) * RT + t.col(ni)] = s * acc[mi][ni][r];
     __syncthreads();
 
     const int rows = min(32, rowsA - wave * 32);                           // uniform; <= 0: nothing
@@ -244,13 +236,9 @@ extern "C" int clipa_topk(const float* Q, const float* G, int64_t Nq, int64_t Ng
   if (workspace_bytes < clipa_topk_workspace(Nq, Ng, k, splits)) { clipa_set_error("topk: workspace too small"); return CLIPA_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   if (S > 0) {
-    const int lds = TK_RING + RT * (int)k * 8;
-    int dev = 0;
-    if (int rc = current_device(&dev)) return rc;
-    if (int rc = g_tk_lds.ensure(dev, {(const void*)topk_tile_kernel}, TK_RING + RT * TK_MAX * 8, "topk")) return rc;
-    hipLaunchKernelGGL(topk_tile_kernel, dim3((unsigned)(tk_tiles(Nq) * S)), dim3(RTHREADS), lds, st, (const char*)Q, (const char*)G,
-                       (int)Nq, (int)Ng, (int)E, (long)ldq, (long)ldg, scale, (int)k, (int)S, (unsigned long long*)workspace);
-    if (int rc = clipa_check_launch("topk_tiles")) return rc;
+    if (int rc = rank_launch(g_tk_lds, {(const void*)topk_tile_kernel}, TK_RING + RT * TK_MAX * 8, "topk", topk_tile_kernel,
+                             tk_tiles(Nq) * S, TK_RING + RT * (int)k * 8, stream, "topk_tiles", (const char*)Q, (const char*)G,
+                             (int)Nq, (int)Ng, (int)E, (long)ldq, (long)ldg, scale, (int)k, (int)S, (unsigned long long*)workspace)) return rc;
   }
   hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((Nq + 3) / 4)), dim3(256), 0, st, (const unsigned long long*)workspace,
                      (int)Nq, (int)k, (int)S, (long)index_base, carry_val, (const long*)carry_idx, out_val, (long*)out_idx);

@@ -25,7 +25,7 @@
 // the lowest class whose value equals the row maximum (both held in LDS).  Which entries of a tile are labels is a 128-bit mask
 // per row, rebuilt from the label list for every tile.  Maxima, minima and integer sums only: no atomics, no workspace, plain
 // stores, and the result does not depend on the order in which lanes meet.
-// LDS: the 64 KiB ring of rank_tile plus 6 KiB of static arrays: two workgroups per CU.
+// LDS: the 64 KiB ring of rank_tile plus 3 KiB of static arrays: two workgroups per CU.
 #include "rank_tile.h"
 
 namespace clipa_gemm {
@@ -63,23 +63,9 @@ __global__ __launch_bounds__(CM_THREADS) void zeroshot_class_mean_kernel(const f
   for (int d = t; d < ldw; d += CM_THREADS) w[d] = d < E ? w[d] / den : 0.f;   // w[d]: this thread's own store
 }
 
-// Recursive halving over the 32 lanes of a lane half (after rank_count, rank_tile.h): x[q] holds this lane's value for row index
-// q = mi * 16 + r; afterwards lane L holds in x[0] the combination of all 32 lanes' values for row index L.
-template <int b, class T, class F>
-__device__ __forceinline__ void halve_step(T (&x)[32], int L, F combine) {
-  const bool up = (L & b) != 0;
-#pragma unroll
-  for (int c = 0; c < b; ++c) {
-    const T lo = x[c], hi = x[c + b];
-    x[c] = combine(up ? hi : lo, __shfl_xor(up ? lo : hi, b, 64));
-  }
-  if constexpr (b > 1) halve_step<b / 2>(x, L, combine);
-}
-template <class T, class F>
-__device__ __forceinline__ void halve32(T (&x)[32], int L, F combine) { halve_step<16>(x, L, combine); }
-
-// offset, within a wave's 64 rows and a lane half's 4-row phase, of the row that value index q = mi * 16 + r belongs to
-__device__ __forceinline__ constexpr int zs_roff(int q) { return (q >> 4) * 32 + (q & 3) + 8 * ((q & 15) >> 2); }
+// what the two column waves of a tile row combine at the end of sweep 1 and of sweep 2 (rank_row_meet)
+struct ZsMax { float best, t; };
+struct ZsOut { int gt, eq, pred; };
 
 __global__ __launch_bounds__(RTHREADS, 2) void zeroshot_ranks_kernel(const char* __restrict__ A, const char* __restrict__ W,
                                                                      const int* __restrict__ labels, int B, int C, int E,
@@ -88,19 +74,14 @@ __global__ __launch_bounds__(RTHREADS, 2) void zeroshot_ranks_kernel(const char*
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ unsigned smask[RT * 4];            // [row][wn][ni]: bit L = class n0 + wn * 64 + ni * 32 + L is a label of the row
   __shared__ float st[RT], sbest[RT];           // t_i and max_c v_ic
-  __shared__ int sx[3][2 * RT];                 // [array][wn][row]: the two column waves' halves of a per-row result
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int L = lane & 31, hi = lane >> 5;
-  const int wm = wave >> 1, wn = wave & 1;
+  const RankLane t = rank_lane();
+  const int tid = t.tid, L = t.L, wn = t.wn;
   const int m0 = blockIdx.x * RT;
-  const int rowsA = min(RT, B - m0);
-  const __amdgpu_buffer_rsrc_t rsA = make_rsrc(A + (size_t)m0 * lda * 4, (unsigned)(rowsA * lda * 4));
+  int rowsA, rowsB;
+  const __amdgpu_buffer_rsrc_t rsA = rank_rows(A, m0, B, lda, &rowsA);
   const int Tc = (C + RT - 1) / RT;
   constexpr int NONE = 0x7fffffff;
   const float ninf = -__builtin_huge_valf();
-  const int rbase = wm * 64 + 4 * hi;           // row of the tile of value index q: rbase + zs_roff(q)
   // this thread's half (64 classes from n0 + 64 * (tid & 1)) of the label mask of row tid / 2; a label outside [0, C) sets nothing
   auto build_mask = [&](int n0) {
     const int row = m0 + (tid >> 1);
@@ -126,17 +107,16 @@ __global__ __launch_bounds__(RTHREADS, 2) void zeroshot_ranks_kernel(const char*
     for (int q = 0; q < 32; ++q) { bv[q] = ninf; tv[q] = ninf; }
     for (int tn = 0; tn < Tc; ++tn) {
       const int n0 = tn * RT;
-      const int rowsB = min(RT, C - n0);
-      const __amdgpu_buffer_rsrc_t rsB = make_rsrc(W + (size_t)n0 * ldw * 4, (unsigned)(rowsB * ldw * 4));
+      const __amdgpu_buffer_rsrc_t rsB = rank_rows(W, n0, C, ldw, &rowsB);
       __syncthreads();                        // the previous tile's readers are done with the ring and with the mask
       build_mask(n0);
       rank_tile(smem, rsA, rsB, lda, ldw, E, acc);      // its first barrier (E >= 1) publishes the mask
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
-        if (n0 + wn * 64 + ni * 32 + L < C) {
+        if (t.col(ni, n0) < C) {
 #pragma unroll
           for (int q = 0; q < 32; ++q) {
-            const unsigned mw = smask[((rbase + zs_roff(q)) * 2 + wn) * 2 + ni];
+            const unsigned mw = smask[(t.row(q) * 2 + wn) * 2 + ni];
             const float v = acc[q >> 4][ni][q & 15];
             bv[q] = v > bv[q] ? v : bv[q];
             tv[q] = ((mw >> L) & 1u) && v > tv[q] ? v : tv[q];
@@ -147,14 +127,10 @@ __global__ __launch_bounds__(RTHREADS, 2) void zeroshot_ranks_kernel(const char*
     auto fmax2 = [](float a, float b) { return b > a ? b : a; };
     halve32(bv, L, fmax2);
     halve32(tv, L, fmax2);
-    const int il = rbase + (L >> 4) * 32 + (L & 3) + 8 * ((L & 15) >> 2);      // rbase + zs_roff(L)
-    sx[0][wn * RT + il] = __float_as_int(bv[0]);
-    sx[1][wn * RT + il] = __float_as_int(tv[0]);
-    __syncthreads();
-    if (tid < RT) {
-      sbest[tid] = fmax2(__int_as_float(sx[0][tid]), __int_as_float(sx[0][RT + tid]));
-      st[tid] = fmax2(__int_as_float(sx[1][tid]), __int_as_float(sx[1][RT + tid]));
-    }
+    __syncthreads();                          // the ring is dead: its first bytes take the two column waves' halves
+    const ZsMax m = rank_row_meet(t, (ZsMax*)smem, ZsMax{bv[0], tv[0]},
+                                  [&](ZsMax a, ZsMax b) { return ZsMax{fmax2(a.best, b.best), fmax2(a.t, b.t)}; });
+    if (tid < RT) { sbest[tid] = m.best; st[tid] = m.t; }
   }
 
   // ---- sweep 2: counts against t_i (gt | eq << 16 per lane and row: at most 2 entries a tile, and the entry point keeps C below 2^20) and the lowest
@@ -164,22 +140,21 @@ __global__ __launch_bounds__(RTHREADS, 2) void zeroshot_ranks_kernel(const char*
   for (int q = 0; q < 32; ++q) { cnt[q] = 0; pc[q] = NONE; }
   for (int tn = 0; tn < Tc; ++tn) {
     const int n0 = tn * RT;
-    const int rowsB = min(RT, C - n0);
-    const __amdgpu_buffer_rsrc_t rsB = make_rsrc(W + (size_t)n0 * ldw * 4, (unsigned)(rowsB * ldw * 4));
+    const __amdgpu_buffer_rsrc_t rsB = rank_rows(W, n0, C, ldw, &rowsB);
     __syncthreads();                          // tn = 0: also publishes st and sbest
     build_mask(n0);
     rank_tile(smem, rsA, rsB, lda, ldw, E, acc);
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) {
-      const int cls = n0 + wn * 64 + ni * 32 + L;
+      const int cls = t.col(ni, n0);
       if (cls < C) {
 #pragma unroll
         for (int q = 0; q < 32; ++q) {
-          const unsigned mw = smask[((rbase + zs_roff(q)) * 2 + wn) * 2 + ni];
-          const float t = st[rbase + zs_roff(q)], best = sbest[rbase + zs_roff(q)];
+          const unsigned mw = smask[(t.row(q) * 2 + wn) * 2 + ni];
+          const float tq = st[t.row(q)], best = sbest[t.row(q)];
           const float v = acc[q >> 4][ni][q & 15];
           const bool lab = (mw >> L) & 1u;
-          cnt[q] += (int)(v > t) + ((int)(!lab && v == t) << 16);
+          cnt[q] += (int)(v > tq) + ((int)(!lab && v == tq) << 16);
           pc[q] = v == best && cls < pc[q] ? cls : pc[q];
         }
       }
@@ -192,19 +167,10 @@ __global__ __launch_bounds__(RTHREADS, 2) void zeroshot_ranks_kernel(const char*
   halve32(cg, L, add2);
   halve32(cnt, L, add2);
   halve32(pc, L, [](int a, int b) { return b < a ? b : a; });
-  __syncthreads();                            // nobody reads sx any more
-  {
-    const int il = rbase + (L >> 4) * 32 + (L & 3) + 8 * ((L & 15) >> 2);
-    sx[0][wn * RT + il] = cg[0];
-    sx[1][wn * RT + il] = cnt[0];
-    sx[2][wn * RT + il] = pc[0];
-  }
-  __syncthreads();
-  if (tid < rowsA) {
-    gt[m0 + tid] = sx[0][tid] + sx[0][RT + tid];
-    eq[m0 + tid] = sx[1][tid] + sx[1][RT + tid];
-    pred[m0 + tid] = min(sx[2][tid], sx[2][RT + tid]);
-  }
+  __syncthreads();                            // the ring is dead
+  const ZsOut o = rank_row_meet(t, (ZsOut*)smem, ZsOut{cg[0], cnt[0], pc[0]},
+                                [](ZsOut a, ZsOut b) { return ZsOut{a.gt + b.gt, a.eq + b.eq, min(a.pred, b.pred)}; });
+  if (tid < rowsA) { gt[m0 + tid] = o.gt; eq[m0 + tid] = o.eq; pred[m0 + tid] = o.pred; }
 }
 
 LdsOptIn g_zs_lds;
@@ -225,11 +191,7 @@ extern "C" int clipa_zeroshot_class_mean(const float* emb, const int32_t* offset
   if (!(eps >= 0.f)) { clipa_set_error("zeroshot_class_mean: eps = %g must be >= 0", (double)eps); return CLIPA_ERR_ARG; }
   if (C == 0) return CLIPA_OK;
   if (N < C) { clipa_set_error("zeroshot_class_mean: N = %ld rows cannot fill C = %ld classes (an empty class has no mean)", (long)N, (long)C); return CLIPA_ERR_ARG; }
-  int i = 0;
-  for (const void* p : {(const void*)emb, (const void*)offsets, (const void*)W}) {
-    if (!p || ((uintptr_t)p & 15)) { clipa_set_error("zeroshot_class_mean: pointer argument %d is null or not 16-byte aligned", i); return CLIPA_ERR_ARG; }
-    ++i;
-  }
+  if (int rc = clipa_check_ptrs16("zeroshot_class_mean", {emb, offsets, W})) return rc;
   hipLaunchKernelGGL(zeroshot_class_mean_kernel, dim3((unsigned)C), dim3(CM_THREADS), 0, (hipStream_t)stream, emb, offsets, (int)N,
                      (int)E, (long)lde, eps, W, (long)ldw);
   return clipa_check_launch("zeroshot_class_mean");
@@ -243,10 +205,7 @@ extern "C" int clipa_zeroshot_ranks(const float* A, const float* W, const int32_
   if (C < 1 || E < 1) { clipa_set_error("zeroshot_ranks: C = %ld classes of E = %ld columns for B = %ld rows (nothing to rank)", (long)C, (long)E, (long)B); return CLIPA_ERR_ARG; }
   if (int rc = rank_check_args("zeroshot_ranks", E, lda, ldw, B >= (1L << 31) - RT || C >= (1L << 20) || B * Lmax >= (1L << 31), "B, C (below 2^20)",
                                {A, W, labels, gt, eq, pred}, nullptr)) return rc;
-  int dev = 0;
-  if (int rc = current_device(&dev)) return rc;
-  if (int rc = g_zs_lds.ensure(dev, {(const void*)zeroshot_ranks_kernel}, 2 * R_STAGE, "zeroshot_ranks")) return rc;
-  hipLaunchKernelGGL(zeroshot_ranks_kernel, dim3((unsigned)((B + RT - 1) / RT)), dim3(RTHREADS), 2 * R_STAGE, (hipStream_t)stream,
-                     (const char*)A, (const char*)W, labels, (int)B, (int)C, (int)E, (int)Lmax, (long)lda, (long)ldw, gt, eq, pred);
-  return clipa_check_launch("zeroshot_ranks");
+  return rank_launch(g_zs_lds, {(const void*)zeroshot_ranks_kernel}, 2 * R_STAGE, "zeroshot_ranks", zeroshot_ranks_kernel,
+                     (B + RT - 1) / RT, 2 * R_STAGE, stream, "zeroshot_ranks", (const char*)A, (const char*)W, labels, (int)B, (int)C,
+                     (int)E, (int)Lmax, (long)lda, (long)ldw, gt, eq, pred);
 }

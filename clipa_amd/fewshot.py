@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._eval_common import _features
 
 
 def class_indices(labels, num_classes, seed):
@@ -20,20 +21,6 @@ def class_indices(labels, num_classes, seed):
     labels = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels)
     rng = np.random.default_rng(seed)
     return [rng.permutation(np.where(labels == c)[0]) for c in range(num_classes)]
-
-
-def _features(t, name, who):
-    if not torch.is_tensor(t) or not t.is_cuda or t.dim() != 2 or not t.dtype.is_floating_point:
-        raise RuntimeError(f"clipa_amd.{who}: {name} must be a 2-D float GPU tensor (no CPU fallback); got "
-                           f"{(t.device, t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
-    t = t.detach().float()
-    if t.shape[0] < 1 or t.shape[1] < 1:
-        raise RuntimeError(f"clipa_amd.{who}: {name} is empty: shape {tuple(t.shape)}")
-    if t.data_ptr() % 16:                          # a misaligned view: one dense copy here instead of one per kernel
-        t = t.clone(memory_format=torch.contiguous_format)
-    if not bool(torch.isfinite(t).all()):
-        raise RuntimeError(f"clipa_amd.{who}: {name} holds non-finite values")
-    return t
 
 
 def _labels(y, n, num_classes, name, who):
@@ -83,7 +70,15 @@ def _task(x, index, counts, x_test, y_test, l2_reg):
 
 
 def _check_problem(x_train, x_test, num_classes, l2_reg, who):
-    x_train, x_test = _features(x_train, "x_train", who), _features(x_test, "x_test", who)
+    feats = []
+    for name, t in (("x_train", x_train), ("x_test", x_test)):
+        t = _features(t, name, who, check_finite=True)
+        if t.shape[0] < 1 or t.shape[1] < 1:
+            raise RuntimeError(f"clipa_amd.{who}: {name} is empty: shape {tuple(t.shape)}")
+        if t.data_ptr() % 16:                      # a misaligned view: one dense copy here instead of one per kernel
+            t = t.clone(memory_format=torch.contiguous_format)
+        feats.append(t)
+    x_train, x_test = feats
     if x_train.shape[1] != x_test.shape[1]:
         raise RuntimeError(f"clipa_amd.{who}: feature widths differ: {x_train.shape[1]} vs {x_test.shape[1]}")
     if int(num_classes) < 1 or not float(l2_reg) > 0.0:

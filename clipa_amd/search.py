@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .zero_shot import _features, unwrap_model
+from ._eval_common import _features, _inference
 
 MAX_K = 32                                    # entries per list the kernel keeps (TK_MAX)
 
@@ -82,19 +82,13 @@ def zero_shot_predict(model, classifier, batches, k=5):
     who = "zero_shot_predict"
     k = _k(k, who)
     w = _features(classifier, "classifier", who)
-    m = unwrap_model(model)
-    was_training = m.training
-    m.eval()
     ids, logits = [], []
-    try:
-        with torch.no_grad():
-            for batch in batches:
-                images = batch[0] if isinstance(batch, (tuple, list)) else batch
-                v, i = topk_similarity(m.encode_image(images, normalize=True), w, k, check_finite=False)
-                ids.append(i)
-                logits.append(v)
-    finally:
-        m.train(was_training)
+    with _inference(model) as m:
+        for batch in batches:
+            images = batch[0] if isinstance(batch, (tuple, list)) else batch
+            v, i = topk_similarity(m.encode_image(images, normalize=True), w, k, check_finite=False)
+            ids.append(i)
+            logits.append(v)
     if not ids:
         raise RuntimeError(f"clipa_amd.{who}: no batches")
     ids, logits = torch.cat(ids), torch.cat(logits)

@@ -16,10 +16,7 @@ import numpy as np
 import torch
 
 from . import ops
-
-
-def unwrap_model(model):                      # zero_shot.py:22-26
-    return model.module if hasattr(model, "module") else model
+from ._eval_common import _features, _inference, unwrap_model
 
 
 @torch.no_grad()
@@ -68,13 +65,6 @@ def run(model, classifier, num_classes, batches, topk=(1, 5)):
 
 # ---- the fused fp32 evaluator (csrc/zeroshot.hip) --------------------------------------------------------------------------
 MAX_LABELS = 32                               # labels per image the rank kernel takes (ZS_MAX_LABELS)
-
-
-def _features(t, name, who):
-    if not torch.is_tensor(t) or not t.is_cuda or t.dim() != 2 or not t.dtype.is_floating_point:
-        raise RuntimeError(f"clipa_amd.{who}: {name} must be a 2-D float GPU tensor (no CPU fallback); got "
-                           f"{(t.device, t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
-    return t.detach().float()
 
 
 def _topk(topk, who):
@@ -140,15 +130,9 @@ def build_classifier(model, prompt_tokens, prompt_class, num_classes, *, text_ba
     _, offsets = prompt_order(prompt_class, num_classes)                   # fail before the towers run
     if int(offsets[-1]) != prompt_tokens.shape[0]:
         raise RuntimeError(f"clipa_amd.{who}: {prompt_tokens.shape[0]} prompts but {int(offsets[-1])} class indices")
-    m = unwrap_model(model)
-    was_training = m.training
-    m.eval()
-    try:
-        with torch.no_grad():
-            emb = torch.cat([m.encode_text(prompt_tokens[i:i + bs], normalize=True).float()
-                             for i in range(0, prompt_tokens.shape[0], bs)])
-    finally:
-        m.train(was_training)
+    with _inference(model) as m:
+        emb = torch.cat([m.encode_text(prompt_tokens[i:i + bs], normalize=True).float()
+                         for i in range(0, prompt_tokens.shape[0], bs)])
     return class_mean_embeddings(emb, prompt_class, num_classes, eps)
 
 
@@ -252,25 +236,19 @@ def evaluate_zero_shot(model, classifier, datasets, topk=(1, 5)):
     ks = _topk(topk, who)
     w = _features(classifier, "classifier", who)
     w_bad = (~torch.isfinite(w)).sum().reshape(1)
-    m = unwrap_model(model)
-    was_training = m.training
-    m.eval()
     results = {}
-    try:
-        with torch.no_grad():
-            for name, batches in datasets.items():
-                total = None
-                for images, labels in batches:
-                    f, _ = _operands(m.encode_image(images, normalize=True), w, who)
-                    stats = _ranks_and_stats(f, w, _labels2d(labels, f.shape[0], f.device, who), ks)[3]
-                    total = stats if total is None else total + stats
-                if total is None:
-                    raise RuntimeError(f"clipa_amd.{who}: dataset {name!r} yielded no batches")
-                total = torch.cat([total, w_bad]).tolist()                 # the dataset's one host sync
-                _raise_on_flags(total, f"{who} ({name})")
-                met = metrics_from_counts(_counts(total, ks), ks)
-                results.update({f"{name}-top{k}": met[f"top{k}"] for k in ks})
-                results[f"{name}-count"] = met["count"]
-    finally:
-        m.train(was_training)
+    with _inference(model) as m:
+        for name, batches in datasets.items():
+            total = None
+            for images, labels in batches:
+                f, _ = _operands(m.encode_image(images, normalize=True), w, who)
+                stats = _ranks_and_stats(f, w, _labels2d(labels, f.shape[0], f.device, who), ks)[3]
+                total = stats if total is None else total + stats
+            if total is None:
+                raise RuntimeError(f"clipa_amd.{who}: dataset {name!r} yielded no batches")
+            total = torch.cat([total, w_bad]).tolist()                 # the dataset's one host sync
+            _raise_on_flags(total, f"{who} ({name})")
+            met = metrics_from_counts(_counts(total, ks), ks)
+            results.update({f"{name}-top{k}": met[f"top{k}"] for k in ks})
+            results[f"{name}-count"] = met["count"]
     return results

@@ -197,6 +197,18 @@ def test_predict_single_class_and_single_row():
     assert _host(pred).tolist() == [0] and _host(best).tolist() == [104.0]
 
 
+def test_predict_writes_every_row_to_its_own_output():
+    """Every row has its own winning logit, n + 1, so a reduction that hands a row's result to another row cannot pass (the
+    planted ties above repeat one value across many rows)."""
+    nt, C, dim = 130, 3, 8
+    n = np.arange(nt)
+    z = np.zeros((nt, dim), dtype=np.int64)
+    z[n, n % C] = n + 1                                    # class n % 3 wins row n with n + 1; the other classes get 0
+    pred, best = ops.fewshot_predict(_dev(z), _dev(np.eye(C, dim, dtype=np.int64)))
+    assert np.array_equal(_host(pred), n % C)
+    assert np.array_equal(_host(best), (n + 1).astype(np.float32))
+
+
 def test_zero_sized_inputs_give_the_empty_computation():
     """The C entry points on zero-sized inputs (include/clipa_hip.h): OK, with what the empty sum or mean is."""
     from clipa_amd import lib
