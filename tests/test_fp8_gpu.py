@@ -402,7 +402,8 @@ def test_fp8_linear_is_close_to_bf16_linear():
     assert bias_rel < 0.005, f"fp8 linear is biased: {bias_rel:.5f}"
 
 
-@pytest.mark.parametrize("D,rows", [(384, 1000), (768, 1000), (1024, 1000), (1280, 1000), (256, 40003)])   # 40003 rows: more than one pass of the 8192-block grid
+@pytest.mark.parametrize("D,rows", [(384, 1000), (768, 1000), (1024, 1000), (1280, 1000), (256, 40003),   # 40003 rows: more than one pass of the 8192-block grid
+                                    (1408, 1000), (1544, 300), (1792, 300), (2048, 300)])   # ViT-g/14; four chunks per lane: one lane of the last (1544), ViT-e/14, all lanes
 def test_layernorm_fwd_q8(D, rows):
     o = ops()
     x = (rnd(rows, D, seed=D, dtype=f32) * 2.0 + 0.3).to(bf16).to(DEV)
@@ -642,6 +643,29 @@ def test_rowscale_max_and_scaled_quantisers():
     assert torch.equal(o.layernorm_fwd_q8s(x.to(DEV), gam, bet, ds.to(DEV), ty, 1e-5), o.scale_quantize_rows(y, ds.to(DEV), ty))
 
 
+@pytest.mark.parametrize("D", [1544, 1792])
+def test_layernorm_quantisers_four_chunks_per_lane(D):
+    """Rows of 1544 - 2048 elements (ViT-bigG/14 1664, ViT-e/14 1792) take the NCH = 4 instantiations of ln_fwd_q8s_kernel and
+    ln_fwd_q8_kernel (1544: one lane active in the last chunk).  The equalities the narrower rows are held to above: the
+    scaled LayerNorm quantiser == LayerNorm (bf16) + the plain scaled quantiser, bit for bit; the row-norm form returns the same
+    y, q, dq as the plain one and ||y||_2 as tests/cpu_ops.layernorm_fwd_q8 states it (test_row_bound_helpers' tolerance)."""
+    o = ops()
+    M = 300
+    g = torch.Generator().manual_seed(D)
+    x = (torch.randn(M, D, generator=g) * torch.exp(torch.randn(M, 1, generator=g))).to(bf16).to(DEV)
+    ds = torch.exp(torch.randn(M, generator=g) * 2.0).float().to(DEV)
+    gam, bet = rnd(D, seed=1, dtype=f32).to(DEV) + 1.0, rnd(D, seed=2, dtype=f32).to(DEV)
+    y = o.layernorm_fwd(x, gam, bet, 1e-5)
+    ty = o.rowscale_max(ds, y.float().abs().amax(1) / 448.0)
+    assert torch.equal(o.layernorm_fwd_q8s(x, gam, bet, ds, ty, 1e-5), o.scale_quantize_rows(y, ds, ty))
+    y2, q2, dq2 = o.layernorm_fwd_q8(x, gam, bet, 1e-5, want_bf16=True)
+    y3, q3, dq3, rn = o.layernorm_fwd_q8(x, gam, bet, 1e-5, want_bf16=True, want_rownorm=True)
+    assert torch.equal(y2, y) and torch.equal(y3, y) and torch.equal(q3, q2) and torch.equal(dq3, dq2)
+    torch.testing.assert_close(rn.cpu(), y.float().norm(dim=1).cpu(), rtol=1e-5, atol=1e-6)
+    _, q4, dq4, rn4 = o.layernorm_fwd_q8(x, gam, bet, 1e-5, want_rownorm=True)
+    assert torch.equal(q4, q2) and torch.equal(dq4, dq2) and torch.equal(rn4, rn)
+
+
 def test_fp8_weight_gradient_recipe_is_close_to_bf16():
     """dW = dY^T X through the recipe of engine._wgrad8 (row-quantised gradient, activation absorbing the row scale, one tensor
     scale) against the fp64 product of the bf16 operands: e4m3 rounding is ~3 % rms per element and averages out over the tokens."""
@@ -814,7 +838,8 @@ def test_gemm_f8a_producer_quantised_outputs(act):
     assert torch.equal(qr, o.scale_quantize_rows(o.gemm_nt_f8(xrq, xrs, wrq, wrs, epi=o.EPI_ACT, act=act), invr, one))
 
 
-@pytest.mark.parametrize("rows,D,fmt", [(1000, 1280, 0), (4099, 1024, 0), (777, 768, 1), (300, 384, 0), (2048, 2048, 1)])
+@pytest.mark.parametrize("rows,D,fmt", [(1000, 1280, 0), (4099, 1024, 0), (777, 768, 1), (300, 384, 0), (2048, 2048, 1),
+                                          (300, 1544, 0), (513, 1792, 1)])      # four chunks per lane with a ragged last one
 def test_layernorm_bwd_with_quantised_output(rows, D, fmt):
     """ops.layernorm_bwd(q8_fmt=...) (clipa_layernorm_bwd_q8, round 6: the LayerNorm backward that hands the next linear layer its
     fp8 gradient operand): dx, dgamma, dbeta (and the emitted LayerNorm output) bit for bit those of the plain backward; q and

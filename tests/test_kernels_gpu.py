@@ -523,7 +523,9 @@ def test_gemm_tn_strided_and_many_slices():
 
 
 # -------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("D", [384, 768, 1024, 1280])
+# 1408 / 1664 / 1792: ViT-g/bigG/e-14 (1664 and up: four 16-byte chunks per lane, NCH = 4); 1544: the narrowest NCH = 4 row, ONE
+# lane active in the last chunk; 2048: every lane.  (f32, f32) is the form of the heads' pooled LayerNorm (engine.py)
+@pytest.mark.parametrize("D", [384, 768, 1024, 1280, 1408, 1544, 1664, 1792, 2048])
 @pytest.mark.parametrize("xdt,ydt", [(bf16, bf16), (f32, bf16), (f32, f32)])
 def test_layernorm(D, xdt, ydt):
     rows = 777
@@ -546,7 +548,8 @@ def test_layernorm(D, xdt, ydt):
     check("dx no-res", dx2, xr.grad, tolx, tolx * 4)
 
 
-@pytest.mark.parametrize("rows,D", [(1, 256), (41, 256), (8190, 256), (300001, 256), (9001, 1280), (5003, 384), (4099, 768), (70001, 1024)])
+@pytest.mark.parametrize("rows,D", [(1, 256), (41, 256), (8190, 256), (300001, 256), (9001, 1280), (5003, 384), (4099, 768), (70001, 1024),
+                                     (1, 2048), (5, 1544), (9001, 1792)])      # NCH = 4: one row, a ragged last chunk, > 1 row per wave
 def test_layernorm_row_counts(rows, D):
     """The launch shapes of layernorm.hip: forward = one block per 8 rows (odd tails), backward = one block per C adjacent rows
     (C = 4 ... 128 by row count) whose dgamma / dbeta partials go through the one- or two-pass reduction (<= / > 128 blocks);
