@@ -8,7 +8,8 @@ get_clip_metrics), multi-caption image-text retrieval (`image_text_retrieval`, `
 linear probe (`fewshot_lsr`, `fewshot_metrics`, `evaluate_fewshot`) and fused fp32 zero-shot classification
 (`build_classifier`, `class_mean_embeddings`, `zero_shot_ranks`, `zero_shot_counts`, `zero_shot_metrics`, `evaluate_zero_shot`)
 and top-k similarity search (`topk_similarity`, `classify_topk`, `zero_shot_predict`, `retrieve_topk`, `knn_classify`,
-`knn_metrics`).
+`knn_metrics`) and the logistic-regression linear probe of Radford et al. 2021 (`fit_logreg`, `logreg_objective`,
+`sweep_l2`, `evaluate_linear_probe`, and `linear_probe.linear_probe` in the module of that name).
 """
 from .configs import add_model_config, get_model_config, list_models
 from .factory import (create_loss, create_model, create_model_and_transforms, get_cast_dtype, load_checkpoint)
@@ -20,6 +21,8 @@ from .data import DeviceAugment, DevicePrefetcher
 from . import fewshot
 from .evaluate import evaluate, get_clip_metrics, metrics_from_ranks
 from .fewshot import evaluate_fewshot, fewshot_lsr, fewshot_metrics
+from . import linear_probe      # the module: its `linear_probe` function is clipa_amd.linear_probe.linear_probe
+from .linear_probe import evaluate_linear_probe, fit_logreg, logreg_objective, sweep_l2
 from .retrieval_eval import evaluate_retrieval, image_text_retrieval
 from .transform import AugmentationCfg, image_transform
 from .zero import ShardedAdamW

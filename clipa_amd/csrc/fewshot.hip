@@ -155,12 +155,6 @@ __global__ __launch_bounds__(64) void fewshot_signsum_kernel(int dim, int C, flo
   for (int c = 0; c < C; ++c) row[c] = 2.0f * row[c] - total;
 }
 
-// A row's running best: the logit and its class (NONE: no class seen yet).  fs_better picks by a strict total order on finite
-// logits - the larger value, equal values by the lower class - so the best of a set does not depend on the order of the meeting.
-struct FsBest { float v; int c; };
-__device__ __forceinline__ FsBest lane_xor(FsBest x, int b) { return {__shfl_xor(x.v, b, 64), __shfl_xor(x.c, b, 64)}; }
-__device__ __forceinline__ FsBest fs_better(FsBest a, FsBest o) { return o.v > a.v || (o.v == a.v && o.c < a.c) ? o : a; }
-
 // One workgroup per 128 test rows, over the class tiles in ascending order.  A lane's accumulator columns are classes
 // tn * 128 + col(ni): ascending in (tn, ni), so per row "replace only on strictly greater" keeps the lowest class of the lane's
 // maxima.  The 64 candidates of a row (32 lanes of each of the two column waves) meet once, at the end (halve32, rank_row_meet);
@@ -174,7 +168,7 @@ __global__ __launch_bounds__(RTHREADS, 2) void fewshot_predict_kernel(const char
   int rowsA, rowsB;
   const __amdgpu_buffer_rsrc_t rsA = rank_rows(Zs, m0, Nt, ldz, &rowsA);
   constexpr int NONE = 0x7fffffff;
-  FsBest best_q[32];
+  RankBest best_q[32];
 #pragma unroll
   for (int q = 0; q < 32; ++q) best_q[q] = {-__builtin_huge_valf(), NONE};
 
@@ -193,14 +187,14 @@ __global__ __launch_bounds__(RTHREADS, 2) void fewshot_predict_kernel(const char
         for (int q = 0; q < 32; ++q) {
           const float v = acc[q >> 4][ni][q & 15];
           const bool take = v > best_q[q].v || best_q[q].c == NONE;
-          best_q[q] = take ? FsBest{v, cls} : best_q[q];
+          best_q[q] = take ? RankBest{v, cls} : best_q[q];
         }
       }
     }
   }
-  halve32(best_q, t.L, fs_better);
+  halve32(best_q, t.L, rank_better);
   __syncthreads();                            // the ring is dead: its first 2 KiB take the two column waves' results
-  const FsBest b = rank_row_meet(t, (FsBest*)smem, best_q[0], fs_better);
+  const RankBest b = rank_row_meet(t, (RankBest*)smem, best_q[0], rank_better);
   if (t.tid < rowsA) {
     pred[m0 + t.tid] = b.c;
     best[m0 + t.tid] = b.v;

@@ -1,5 +1,5 @@
 // The 128 x 128 fp32 similarity tile of the evaluation kernels (retrieval.hip, retrieval_multi.hip, fewshot.hip, zeroshot.hip,
-// topk.hip) and what every consumer of it needs: one copy, so every x_ij = A_i . B_j comes out of the same instruction sequence
+// topk.hip, logreg.hip) and what every consumer of it needs: one copy, so every x_ij = A_i . B_j comes out of the same instruction sequence
 // whichever kernel, launch or tile computes it.  That is what lets a positive compare with itself exactly (retrieval.hip) and
 // what tests/test_retrieval_multi_gpu.py and tests/test_topk_gpu.py check between the kernels bit for bit.
 //   RankLane        a lane's place in the tile: the only copy of the D-fragment map (row(q), col(ni))
@@ -7,6 +7,7 @@
 //   rank_tile       the main loop
 //   halve32, rank_row_meet   per-row reduction over the 64 lanes that share a tile row: 32 lanes of a wave, then the two column waves
 //   rank_count      the count epilogue of the two retrieval kernels
+//   RankBest, rank_better    a row's running (logit, class) best and its order-free meeting
 //   f32_key / f32_unkey      order-preserving float <-> unsigned map (integer atomicMax, sort keys)
 //   rank_check_args, rank_launch   host side: argument checks and the launch on the 2 x R_STAGE ring
 //
@@ -168,6 +169,13 @@ __device__ __forceinline__ T rank_row_meet(const RankLane& t, T* buf, T x, F com
   const int i = t.tid & (RT - 1);
   return combine(buf[i], buf[RT + i]);
 }
+
+// A row's running best of the argmax kernels (fewshot.hip, logreg.hip): the logit and its class (c = 0x7fffffff: no class seen
+// yet).  rank_better picks by a strict total order on finite logits - the larger value, equal values by the lower class - so the
+// best of a set does not depend on the order of the meeting.
+struct RankBest { float v; int c; };
+__device__ __forceinline__ RankBest lane_xor(RankBest x, int b) { return {__shfl_xor(x.v, b, 64), __shfl_xor(x.c, b, 64)}; }
+__device__ __forceinline__ RankBest rank_better(RankBest a, RankBest o) { return o.v > a.v || (o.v == a.v && o.c < a.c) ? o : a; }
 
 // Count epilogue of the tile at (m0, n0) with rowsA x rowsB valid entries, v = fl(s * acc): per row i the entries that beat
 // (gt) or tie (eq) the row's positive, per column j those against the column's positive, added atomically to

@@ -96,6 +96,11 @@ SIGNATURES = {
     "clipa_fewshot_gram": (_I32, [_P, _I64, _I64, _I64, _P, _I64, _P]),
     "clipa_fewshot_class_sums": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _P, _I64, _P]),
     "clipa_fewshot_predict": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _P]),
+    "clipa_logreg_prepare": (_I32, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P]),
+    "clipa_logreg_logits": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _P, _P, _P, _P]),
+    "clipa_logreg_residual": (_I32, [_P, _P, _P, _I64, _I64, _I64, _P, _I32, _P]),
+    "clipa_logreg_grad_workspace": (_I64, [_I64, _I64, _I64, _I64]),
+    "clipa_logreg_grad": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _P]),
     "clipa_zeroshot_class_mean": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _F, _P, _I64, _P]),
     "clipa_zeroshot_ranks": (_I32, [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
     "clipa_topk_workspace": (_I64, [_I64, _I64, _I64, _I64]),

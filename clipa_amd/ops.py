@@ -1272,6 +1272,93 @@ def fewshot_predict(z, w):
     return out_p[:Nt], out_b[:Nt]
 
 
+LOGREG_MAX_N = 1 << 21      # csrc/logreg.hip: a 128-class block of the [C, N] logits stays below 1 GiB
+
+
+def logreg_prepare(x):
+    """The operands of the logistic-regression probe (csrc/logreg.hip), once per fit: x f32 [N, D] -> (xp, xt), xp the
+    [N, D + 1] view of a [N, D + 1 rounded up to 4] buffer holding [x, 1] and zeros, xt the [D + 1, N] view of its transpose in
+    a [D + 1, N rounded up to 4] buffer padded the same way."""
+    x, ldx, _, N = _fewshot_rows(x, None, "logreg_prepare")
+    D = x.shape[1]
+    if N < 1 or N >= LOGREG_MAX_N:
+        raise RuntimeError(f"logreg_prepare: N = {N} rows must lie in [1, 2^21 = {LOGREG_MAX_N}) (features that do not fit one "
+                           f"problem are not supported)")
+    dim = D + 1
+    pb = torch.empty((N, (dim + 3) // 4 * 4), device=x.device, dtype=f32)
+    tb = torch.empty((dim, (N + 3) // 4 * 4), device=x.device, dtype=f32)
+    with _Timed("logreg_prepare", 0.0, 12.0 * N * dim):
+        lib.call("clipa_logreg_prepare", _p(x), N, D, ldx, _p(pb), pb.shape[1], _p(tb), tb.shape[1], _stream())
+    return pb[:, :dim], tb[:, :N]
+
+
+def _logreg_view(t, name, rows=None, cols=None):
+    """A matrix the logreg kernels take as it is: f32 [rows, cols], unit column stride, 16-byte aligned rows."""
+    _chk(t, f32, name, 2)
+    ld = t.stride(0) if t.shape[0] > 1 else (t.shape[1] + 3) // 4 * 4
+    if t.stride(1) != 1 or ld % 4 or t.data_ptr() % 16 or ld < t.shape[1]:
+        raise RuntimeError(f"clipa_amd.ops: {name} must have unit column stride and 16-byte aligned rows (as logreg_prepare / "
+                           f"logreg_logits return it); got strides {tuple(t.stride())}")
+    if (rows is not None and t.shape[0] != rows) or (cols is not None and t.shape[1] != cols):
+        raise RuntimeError(f"clipa_amd.ops: {name} must be [{rows}, {cols}], got {tuple(t.shape)}")
+    return ld
+
+
+def logreg_logits(theta, xp, out=None):
+    """theta f32 [C, dim] (class-major, the last column the bias), xp [N, dim] of logreg_prepare -> (zt, lse, pred, best):
+    zt the [C, N] view of a [C, N rounded up to 4] buffer (`out`: such a view to write into, from an earlier call), zt[c, n] =
+    theta_c . xp_n; lse f32 [N] = log sum_c exp zt[c, n]; pred int32 [N] / best f32 [N]: the lowest class among a sample's
+    maxima and that logit, as fewshot_predict(xp, theta) gives them bit for bit."""
+    _chk(theta, f32, "theta", 2)
+    if theta.shape[0] < 1 or theta.shape[1] < 1 or xp.dim() != 2 or theta.shape[1] != xp.shape[1]:
+        raise RuntimeError(f"logreg_logits: theta {tuple(theta.shape)} and xp {tuple(xp.shape)} must be [C >= 1, dim] and [N, dim]")
+    theta, ldt = _aligned_rows(theta)
+    C, dim = theta.shape
+    N = xp.shape[0]
+    ld = _logreg_view(xp, "xp")
+    if N < 1 or N >= LOGREG_MAX_N:
+        raise RuntimeError(f"logreg_logits: N = {N} rows must lie in [1, 2^21 = {LOGREG_MAX_N})")
+    zt = torch.empty((C, (N + 3) // 4 * 4), device=xp.device, dtype=f32)[:, :N] if out is None else out
+    ldz = _logreg_view(zt, "out", C, N)
+    vec = torch.empty((3, (N + 3) // 4 * 4), device=xp.device, dtype=f32)
+    pred = vec[1].view(torch.int32)
+    with _Timed("logreg_logits", 2.0 * N * C * dim, 4.0 * (N * C + N * dim + C * dim)):
+        lib.call("clipa_logreg_logits", _p(theta), _p(xp), C, N, dim, ldt, ld, _p(zt), ldz, _p(vec[0]), _p(pred), _p(vec[2]),
+                 _stream())
+    return zt, vec[0, :N], pred[:N], vec[2, :N]
+
+
+def logreg_residual(zt, lse, y, overwrite=True):
+    """ce[n] = lse[n] - zt[y_n, n]; with overwrite, then in place zt[c, n] <- exp(zt[c, n] - lse[n]) - [c == y_n].  zt, lse of
+    logreg_logits; y int32 GPU tensor [N] with values in [0, C) (a value outside gives ce = NaN).  -> ce f32 [N]."""
+    C, N = zt.shape
+    ldz = _logreg_view(zt, "zt")
+    if not torch.is_tensor(y) or not y.is_cuda or y.dtype != torch.int32 or tuple(y.shape) != (N,):
+        raise RuntimeError(f"logreg_residual: y must be an int32 GPU tensor of {N} labels")
+    lse, y = _vec16(lse, N, "lse"), (y.contiguous() if y.data_ptr() % 16 == 0 and y.is_contiguous() else y.clone())
+    ce = torch.empty((N + 3) // 4 * 4, device=zt.device, dtype=f32)
+    with _Timed("logreg_residual", 0.0, (8.0 if overwrite else 0.0) * N * C + 16.0 * N):
+        lib.call("clipa_logreg_residual", _p(zt), _p(lse), _p(y), C, N, ldz, _p(ce), 1 if overwrite else 0, _stream())
+    return ce[:N]
+
+
+def logreg_grad(gt, xt, _slice=0, _max_workgroups=0):
+    """dtheta[c, d] = sum_n gt[c, n] * xt[d, n]: gt f32 [C, N] (the residual), xt [dim, N] of logreg_prepare -> f32 [C, dim].
+    n runs in slices of 4096 samples, each an ascending-n fp32 chain, the slices added in ascending order: bit-identical
+    whatever the launch.  _slice / _max_workgroups: tests only - another slice length (another, equally fixed, summation
+    order) and a cap on the grid (no effect on any bit)."""
+    C, N = gt.shape
+    ldz = _logreg_view(gt, "gt")
+    ldn = _logreg_view(xt, "xt", None, N)
+    dim = xt.shape[0]
+    out = torch.empty((C, (dim + 3) // 4 * 4), device=gt.device, dtype=f32)
+    ws, wsb = _workspace("clipa_logreg_grad_workspace", C, dim, N, int(_slice), device=gt.device, floor=16)
+    with _Timed("logreg_grad", 2.0 * N * C * dim, 4.0 * (N * C + N * dim + C * dim)):
+        lib.call("clipa_logreg_grad", _p(gt), _p(xt), C, dim, N, ldz, ldn, _p(out), out.shape[1], int(_slice),
+                 int(_max_workgroups), _p(ws), wsb, _stream())
+    return out[:, :dim]
+
+
 def zeroshot_class_mean(emb, offsets, eps=0.0):
     """The prompt-ensemble classifier of zero-shot classification (zero_shot.py:37-38; _average_embeddings of
     discriminative_classifier.py:165-170): emb f32 [N, E] with its rows sorted by class, offsets the C + 1 segment bounds (host

@@ -382,6 +382,43 @@ int clipa_fewshot_class_sums(const float* Z, const int32_t* offsets, int64_t N, 
  * pred[n] = the lowest class index among the maxima of row n, best[n] = that logit (finite logits assumed). */
 int clipa_fewshot_predict(const float* Z, const float* W, int64_t Nt, int64_t C, int64_t dim, int64_t ldz, int64_t ldw,
                           int32_t* pred, float* best, void* stream);
+/* Logistic-regression linear probe (Radford et al. 2021, "Learning Transferable Visual Models From Natural Language
+ * Supervision", section 3.2 and appendix A.3: an L2-regularised multinomial logistic regression on frozen image features, fitted
+ * with L-BFGS; the reference has no such evaluator, so the paper is cited where its lines would be).  One objective-and-gradient
+ * evaluation at theta [C, dim], dim = D + 1, class-major, the last column the bias; x~_n = [x_n, 1]:
+ *   f_data = (1 / N) sum_n (lse_n - z_{n, y_n}),  z_n = theta x~_n,  lse_n = log sum_c exp z_{n, c}        (A.3)
+ *   d f_data / d theta = (1 / N) (softmax(z) - onehot(y))^T X~
+ * The kernels compute the sums; the 1 / N, the sum over n of ce and the L2 term are the caller's (fp64 on the host).  Everything
+ * fp32, every reduction in a fixed order (no float atomics: results bit-reproducible whatever the grid); pointers 16-byte
+ * aligned, matrices row-major, leading dimensions multiples of 4.  N < 2^21 (a 128-class block of the [C, N] logits stays below
+ * 1 GiB), C <= 65535, dim < 2^21; CLIPA_ERR_ARG with a message otherwise.  Zero sizes return CLIPA_OK where the result is empty
+ * (N = 0 for prepare, logits and residual; C = 0 or dim = 0 for grad; grad over N = 0 samples gives dtheta = 0); C = 0 with
+ * N > 0 is CLIPA_ERR_ARG for logits and residual.
+ * prepare: Xp [N, ld] = [x, 1] with columns (D, ld) = 0, and Xt [D + 1, ldn] = its transpose with columns [N, ldn) = 0; x [N, ldx],
+ * ld >= D + 1, ldn >= N.  Once per fit. */
+int clipa_logreg_prepare(const float* x, int64_t N, int64_t D, int64_t ldx, float* Xp, int64_t ld, float* Xt, int64_t ldn,
+                         void* stream);
+/* logits: Zt [C, ldz >= N], Zt[c, n] = theta_c . x~_n by the arithmetic of clipa_fewshot_gram (theta [C, ldt], Xp [N, ld] of
+ * prepare), columns [N, ldz) untouched; lse[n] = log sum_c exp Zt[c, n]; pred[n] = the lowest class among the maxima of column
+ * n, best[n] = that logit (both equal clipa_fewshot_predict on the same operands bit for bit).  lse keeps, per sample and
+ * 128-class tile, a running (m, s): m' = max(m, max_c v_c), s = s exp(m - m') + sum_c exp(v_c - m') with c ascending inside a
+ * lane's 32 classes of the tile, expf / logf; the 4 partial results of a sample meet in a fixed order. */
+int clipa_logreg_logits(const float* theta, const float* Xp, int64_t C, int64_t N, int64_t dim, int64_t ldt, int64_t ld, float* Zt,
+                        int64_t ldz, float* lse, int32_t* pred, float* best, void* stream);
+/* residual: ce[n] = lse[n] - Zt[y_n, n] (the sample's cross entropy), then, with overwrite != 0, in place
+ * Zt[c, n] <- expf(Zt[c, n] - lse[n]) - [c == y_n] (softmax minus one-hot: Gt).  overwrite = 0 writes ce alone (a line-search
+ * probe).  y int32 [N] in DEVICE memory; a label outside [0, C) gives ce[n] = NaN and is not used as an index. */
+int clipa_logreg_residual(float* Zt, const float* lse, const int32_t* y, int64_t C, int64_t N, int64_t ldz, float* ce,
+                          int32_t overwrite, void* stream);
+/* grad: dtheta [C, ldg >= dim], dtheta[c, d] = sum_n Gt[c, n] Xt[d, n] (Gt [C, ldz] of residual, Xt [dim, ldn] of prepare),
+ * columns [dim, ldg) untouched.  n is cut into slices of `slice` samples (0: the default 4096; a multiple of 4 - a constant of
+ * the algorithm, not of the launch: another value changes the last bits); each slice's product is one ascending-n fp32 chain
+ * per entry, and the slices' partials are added in ascending order.  max_workgroups (0: no limit) caps the grid and changes no
+ * bit.  Workspace: clipa_logreg_grad_workspace(C, dim, N, slice) bytes (0 for a single slice). */
+int64_t clipa_logreg_grad_workspace(int64_t C, int64_t dim, int64_t N, int64_t slice);
+int clipa_logreg_grad(const float* Gt, const float* Xt, int64_t C, int64_t dim, int64_t N, int64_t ldz, int64_t ldn,
+                      float* dtheta, int64_t ldg, int64_t slice, int64_t max_workgroups, void* workspace,
+                      int64_t workspace_bytes, void* stream);
 /* Zero-shot classification (clipa_torch/training/zero_shot.py:29-90; clipa_jax/evaluators/proj/image_text/
  * discriminative_classifier.py:152-171, 302-312).  Everything fp32, every reduction in a fixed order (no float atomics, results
  * bit-reproducible); pointers 16-byte aligned, matrices row-major.
