@@ -132,6 +132,19 @@ def _aligned_rows(x):
     return x, ld
 
 
+def _aligned16(t):
+    """A [rows, E] bf16 operand of the similarity-loss kernels -> (tensor, ld).  Their global -> LDS loads move 16 bytes per lane:
+    next to ld % 8 == 0 (checked on the C side) the first element has to be 16-byte aligned, which a column slice at an offset
+    that is no multiple of 8 (buf[:, 4:76]) is not.  Such a view is copied, as _aligned_rows does for the eval kernels."""
+    t, ld = _rowmajor(t)
+    if t.data_ptr() % 16:
+        t = t.contiguous()
+        if t.data_ptr() % 16:      # dense already, at an odd offset of its buffer
+            t = t.clone()
+        ld = t.shape[1]
+    return t, ld
+
+
 def _scalar1(scale):
     """An optional f32 device scalar as the contiguous [1] tensor the kernels read."""
     if scale is None:
@@ -976,13 +989,14 @@ def activation_fwd(x, act):
 
 def simce(rows, cols, n_valid, label0, gscale, scale=None, want_grad=True):
     """Fused similarity + cross-entropy (InfoNCE): logits = s * rows @ cols[:n_valid]^T, labels label0 + row; s =
-    scale[0] read on the device (None = 1).  rows [R,E], cols [>= n_valid, E] bf16.  Returns loss_rows f32 [R], the bf16
+    scale[0] read on the device (None = 1).  rows [R,E], cols [>= n_valid, E] bf16, row-major views with ld % 8 == 0 (a view
+    whose first element is not 16-byte aligned is copied).  Returns loss_rows f32 [R], the bf16
     d loss / d (rows @ cols^T) [R, n8] (n8 = n_valid rounded up to 8, pad columns zero) | None, and the per-row
     d loss / d s.  The fp32 logits never exist in HBM (the backward re-runs the similarity GEMM)."""
     _chk(rows, bf16, "rows", 2)
     _chk(cols, bf16, "cols", 2)
-    rows, lda = _rowmajor(rows)
-    cols, ldb = _rowmajor(cols)
+    rows, lda = _aligned16(rows)
+    cols, ldb = _aligned16(cols)
     R, E = rows.shape
     if cols.shape[1] != E or cols.shape[0] < n_valid:
         raise RuntimeError(f"simce: cols {tuple(cols.shape)} does not cover {n_valid} x {E}")
@@ -1014,8 +1028,8 @@ def simsig(rows, cols, n_valid, label0, gscale, scale, bias, want_grad=True):
     _chk(cols, bf16, "cols", 2)
     _chk(scale, f32, "scale")
     _chk(bias, f32, "bias")
-    rows, lda = _rowmajor(rows)
-    cols, ldb = _rowmajor(cols)
+    rows, lda = _aligned16(rows)
+    cols, ldb = _aligned16(cols)
     R, E = rows.shape
     if cols.shape[1] != E or cols.shape[0] < n_valid:
         raise RuntimeError(f"simsig: cols {tuple(cols.shape)} does not cover {n_valid} x {E}")
@@ -1037,10 +1051,10 @@ def simsig(rows, cols, n_valid, label0, gscale, scale, bias, want_grad=True):
 def _distill_operands(rows_s, cols_s, rows_t, cols_t, n_valid, scale_s, scale_t, extra=()):
     for t, name in ((rows_s, "rows_s"), (cols_s, "cols_s"), (rows_t, "rows_t"), (cols_t, "cols_t")):
         _chk(t, bf16, name, 2)
-    rows_s, ldas = _rowmajor(rows_s)
-    cols_s, ldbs = _rowmajor(cols_s)
-    rows_t, ldat = _rowmajor(rows_t)
-    cols_t, ldbt = _rowmajor(cols_t)
+    rows_s, ldas = _aligned16(rows_s)
+    cols_s, ldbs = _aligned16(cols_s)
+    rows_t, ldat = _aligned16(rows_t)
+    cols_t, ldbt = _aligned16(cols_t)
     R, Es = rows_s.shape
     Et = rows_t.shape[1]
     if rows_t.shape[0] != R:

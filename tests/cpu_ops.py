@@ -306,7 +306,23 @@ def activation_fwd(x, act):
     return _act(x.float(), act).to(bf16)
 
 
+def _chk_sim(who, rows, cols, n_valid, label0):
+    """The argument errors of the similarity-loss wrappers and of their C entry points (ce_check / dce_check)."""
+    R, E = rows.shape
+    if cols.shape[1] != E or cols.shape[0] < n_valid:
+        raise RuntimeError(f"{who}: cols {tuple(cols.shape)} does not cover {n_valid} x {E}")
+    if E <= 0 or E % 8 or (R > 1 and rows.stride(0) % 8) or (cols.shape[0] > 1 and cols.stride(0) % 8):
+        raise RuntimeError(f"{who}: E, lda, ldb must be multiples of 8")
+    if label0 < 0 or label0 + R > n_valid:
+        raise RuntimeError(f"{who}: labels [{label0}, {label0 + R}) outside [0, {n_valid})")
+
+
+def _scalar(t):
+    return float(t.reshape(-1)[0]) if t is not None else 1.0
+
+
 def simce(rows, cols, n_valid, label0, gscale, scale=None, want_grad=True):
+    _chk_sim("simce", rows, cols, n_valid, label0)
     R = rows.shape[0]
     n8 = (n_valid + 7) // 8 * 8
     s = float(scale.reshape(-1)[0]) if scale is not None else 1.0
@@ -322,6 +338,62 @@ def simce(rows, cols, n_valid, label0, gscale, scale=None, want_grad=True):
     dl = torch.zeros((R, n8), dtype=bf16)
     dl[:, :n_valid] = (g * s).to(bf16)
     return loss_rows, dl, (g * raw).sum(1)
+
+
+def simsig(rows, cols, n_valid, label0, gscale, scale, bias, want_grad=True):
+    _chk_sim("simsig", rows, cols, n_valid, label0)
+    if scale.numel() != 1 or bias.numel() != 1:
+        raise RuntimeError(f"simsig: scale and bias are scalars, got {tuple(scale.shape)} and {tuple(bias.shape)}")
+    R = rows.shape[0]
+    n8 = (n_valid + 7) // 8 * 8
+    s, b = _scalar(scale), _scalar(bias)
+    raw = rows.float() @ cols[:n_valid].float().T
+    y = -torch.ones(R, n_valid)
+    y[torch.arange(R), torch.arange(R) + label0] = 1.0
+    t = y * (s * raw + b)
+    loss_rows = torch.nn.functional.softplus(-t).sum(1)
+    if not want_grad:
+        return loss_rows, None, None, None
+    gg = gscale * (-y) * torch.sigmoid(-t)
+    dl = torch.zeros((R, n8), dtype=bf16)
+    dl[:, :n_valid] = (gg * s).to(bf16)
+    return loss_rows, dl, (gg * raw).sum(1), gg.sum(1)
+
+
+def _chk_distill(rows_s, cols_s, rows_t, cols_t, n_valid, label0):
+    if rows_t.shape[0] != rows_s.shape[0]:
+        raise RuntimeError(f"simce_distill: teacher rows {tuple(rows_t.shape)} vs student rows {tuple(rows_s.shape)}")
+    _chk_sim("simce_distill", rows_s, cols_s, n_valid, label0)
+    _chk_sim("simce_distill", rows_t, cols_t, n_valid, label0)
+
+
+def simce_distill(rows_s, cols_s, rows_t, cols_t, n_valid, label0, scale_s=None, scale_t=None):
+    _chk_distill(rows_s, cols_s, rows_t, cols_t, n_valid, label0)
+    R = rows_s.shape[0]
+    z = (rows_s.float() @ cols_s[:n_valid].float().T) * _scalar(scale_s)
+    y = (rows_t.float() @ cols_t[:n_valid].float().T) * _scalar(scale_t)
+    lse_s, lse_t = torch.logsumexp(z, dim=1), torch.logsumexp(y, dim=1)
+    ce_rows = lse_s - z[torch.arange(R), torch.arange(R) + label0]
+    dist_rows = lse_s - (torch.softmax(y, dim=1) * z).sum(1)
+    return ce_rows, dist_rows, lse_s, lse_t
+
+
+def simce_distill_bwd(rows_s, cols_s, rows_t, cols_t, n_valid, label0, gscale, lse_s, lse_t, scale_s=None, scale_t=None,
+                      g_c=None, g_d=None):
+    """As the kernel: the probabilities are exp(logit - lse) of the forward's log-sum-exps."""
+    _chk_distill(rows_s, cols_s, rows_t, cols_t, n_valid, label0)
+    R = rows_s.shape[0]
+    n8 = (n_valid + 7) // 8 * 8
+    s = _scalar(scale_s)
+    raw = rows_s.float() @ cols_s[:n_valid].float().T
+    ps = torch.exp(raw * s - lse_s[:, None])
+    pt = torch.exp((rows_t.float() @ cols_t[:n_valid].float().T) * _scalar(scale_t) - lse_t[:, None])
+    oh = torch.zeros(R, n_valid)
+    oh[torch.arange(R), torch.arange(R) + label0] = 1.0
+    gg = (_scalar(g_c) * gscale) * (ps - oh) + (_scalar(g_d) * gscale) * (ps - pt)
+    dl = torch.zeros((R, n8), dtype=bf16)
+    dl[:, :n_valid] = (gg * s).to(bf16)
+    return dl, (gg * raw).sum(1)
 
 
 def sum_scale(x, scale, out=None, accumulate=False):

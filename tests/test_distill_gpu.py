@@ -12,6 +12,8 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 import torch.nn.functional as F
 
+from .loss_cases import DL_RTOL, KAPPA_FLOOR, kappa_rule
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "distill_loss.npz")
 DEV = torch.device("cuda", 0)
@@ -33,7 +35,7 @@ def _cos(a, b):
 def _fp64_direction(As, Bs, At, Bt, N, label0, s, u, gs, gc, gd):
     """fp64 restatement of one direction, computed in row chunks on the device (no [R, N] fp32 logits needed anyway)."""
     R = As.shape[0]
-    out = {k: [] for k in ("lse_s", "lse_t", "ce", "dist", "dl", "ds", "ds_abs")}
+    out = {k: [] for k in ("lse_s", "lse_t", "ce", "dist", "dl", "mag", "ds", "ds_abs")}
     Bs64, Bt64 = Bs[:N].double(), Bt[:N].double()
     for r0 in range(0, R, 512):
         r1 = min(R, r0 + 512)
@@ -49,14 +51,24 @@ def _fp64_direction(As, Bs, At, Bt, N, label0, s, u, gs, gc, gd):
         out["lse_t"].append(lt)
         out["ce"].append(ls - z.gather(1, lab[:, None])[:, 0])
         out["dist"].append(ls - (pt * z).sum(1))
-        out["dl"].append((s * gl).float())
+        out["dl"].append(s * gl)
+        out["mag"].append(s * gs * (gc * (ps + oh) + gd * (ps + pt)))     # the terms whose difference dl is (loss_cases.py)
         out["ds"].append((gl * raw).sum(1))
         out["ds_abs"].append((gl * raw).abs().sum(1))        # the scale of the cancelling sum, for its tolerance
     return {k: torch.cat(v) for k, v in out.items()}
 
 
-@pytest.mark.parametrize("R,N", [(64, 64), (100, 100), (64, 100), (257, 257), (1000, 1000), (4096, 4096 * 8)])
+# (R, N) -> the kappa of tests/loss_cases.py's element-wise dl comparison that the fp32 stand-in (tests/cpu_ops) needs on
+# these inputs against fp64; the kernel is held to kappa_rule of it (4 x, floored at 2^-20).  The teacher logits reach
+# |y| ~ 20 here (u = 100 on raw similarities ~ 0.15), for which 2^-22 |y| predicts 4.8e-6.
+DISTILL_KAPPA_FP32 = {(64, 64): 0.0, (100, 100): 0.0, (64, 100): 0.0, (257, 257): 0.0, (1000, 1000): 2.33e-6,
+                      (4096, 4096 * 8): 2.21e-6}
+
+
+@pytest.mark.parametrize("R,N", list(DISTILL_KAPPA_FP32))
 def test_simce_distill_kernel_matches_fp64(R, N):
+    """dl is compared element by element, |got - ref| <= 2^-7 |ref| + kappa mag: a bound relative to max |dl| (the diagonal
+    term) lets an off-diagonal entry, about 1 / N of it, be wrong by 100 %."""
     from clipa_amd import ops
     Es, Et = 512, 768
     label0 = N - R if N != R else 0
@@ -82,10 +94,11 @@ def test_simce_distill_kernel_matches_fp64(R, N):
     assert dl.shape == (R, n8)
     if n8 > N:
         assert (dl[:, N:] == 0).all(), "pad columns of dl must be zero"
-    d = dl[:, :N].float()
-    scale = want["dl"].abs().max().item()
-    assert (d - want["dl"]).abs().max().item() < 1e-2 * scale + 1e-6 * s_val
-    assert _cos(d, want["dl"]) > 0.9999
+    kappa = kappa_rule(DISTILL_KAPPA_FP32[(R, N)])
+    assert kappa >= KAPPA_FLOOR
+    ratio = (dl[:, :N].double() - want["dl"]).abs() / (DL_RTOL * want["dl"].abs() + kappa * want["mag"])
+    print(f"[distill kernel {R}x{N}] dl: worst error / tolerance {ratio.max().item():.3g}")
+    assert ratio.max().item() <= 1.0, (ratio.max().item(), divmod(int(ratio.argmax()), N))
     err_ds = (ds.double() - want["ds"]).abs().max().item()
     assert err_ds < 1e-4 * want["ds_abs"].max().item() + 1e-7, err_ds
     # deterministic: a second call is bitwise equal
