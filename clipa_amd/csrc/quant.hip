@@ -7,14 +7,9 @@
 // no atomics), so a block's backward-time recompute reproduces its forward bit for bit.
 // HBM-bound: one wave per row, the row stays in registers between the max and the convert (2 B read + 1 B written
 // per element); the LayerNorm variant emits the fp8 operand of the following GEMM straight from the normalised row.
-#include "common.h"
-#include "stream.h"
-#include "quant_common.h"
+#include "row_wave.h"
 #include "clipa_hip.h"
 
-#ifndef LN_Q8_PREFETCH
-#define LN_Q8_PREFETCH 1                          // A/B knob (tools/stream8_bench.py --lib)
-#endif
 #ifndef LN_Q8_BLOCK_CAP
 #define LN_Q8_BLOCK_CAP 8192                      // A/B knob (tools/stream_lib_ab.py)
 #endif
@@ -25,37 +20,18 @@ namespace {
 template <int NCH, int FMT>
 __global__ __launch_bounds__(256) void quantize_rows_kernel(const char* __restrict__ x, long ldx, char* __restrict__ q, long ldq,
                                                             float* __restrict__ dq, long rows, int K) {
-  const int lane = threadIdx.x & 63;
+  const RowWave<NCH> w(K);
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const int nchunks = K >> 3;
-  u32x4 v[NCH];
-  float amax = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int ch = lane + c * 64;
-    v[c] = u32x4{0, 0, 0, 0};
-    if (ch < nchunks) {
-      v[c] = ld_stream<u32x4>(x + ((size_t)row * ldx + (size_t)ch * 8) * 2);
-      float f[8];
-      unpack8(v[c], f);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(f[i]));
-    }
-  }
-  amax = wave_max(amax);
-  float s, d;
-  row_scales<FMT>(amax, s, d);
-  if (lane == 0) dq[row] = d;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int ch = lane + c * 64;
-    if (ch < nchunks) {
-      float f[8];
-      unpack8(v[c], f);
-      st_stream<u32x2>(q + (size_t)row * ldq + (size_t)ch * 8, cvt8<FMT>(f, s));
-    }
-  }
+  u32x4 v[NCH] = {};
+  RowMag m;
+  w.each([&](int c, size_t col) {
+    v[c] = ld_row8(x, (size_t)row * ldx + col);
+    float f[8];
+    unpack8(v[c], f);
+    m.add8(f);
+  });
+  quantize_row<FMT>(w, v, m, q + (size_t)row * ldq, dq, nullptr, row);
 }
 
 // quantize_rows_kernel that also sums the COLUMNS of x (the bias gradient of the layer whose input gradient consumes q: the
@@ -67,62 +43,36 @@ __global__ __launch_bounds__(256) void quantize_rows_colsum_kernel(const char* _
                                                                    float* __restrict__ dq, float* __restrict__ partial, float* __restrict__ rnorm,
                                                                    long rows, int K) {
   __shared__ float red[4][512];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const RowWave<NCH> w(K);
+  const int lane = w.lane, wave = threadIdx.x >> 6;
   const long wid = (long)blockIdx.x * 4 + wave;
   const long nw = (long)gridDim.x * 4;
-  const int nchunks = K >> 3;
-  float cs[NCH][8];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) cs[c][i] = 0.f;
+  float cs[NCH][8] = {};
   // The next row's loads are issued before this row's arithmetic (two rows in flight per wave, as the LayerNorm + quantise
   // kernels) where that fits the register file: hipcc needs 206 / 254 / 290 registers for the 6 / 8 / 16-chunk instantiations
   // with the second row (two waves per SIMD: 3.5 TB/s at K = 3840 instead of 5.4), 98 and 183 for 4 and 10 chunks.
   constexpr bool PF = NCH <= 4 || NCH == 10;
-  u32x4 nxt[PF ? NCH : 1];
+  u32x4 nxt[PF ? NCH : 1] = {};
   if constexpr (PF) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int ch = lane + c * 64;
-      nxt[c] = u32x4{0, 0, 0, 0};
-      if (ch < nchunks && wid < rows) nxt[c] = ld_stream<u32x4>(x + ((size_t)wid * ldx + (size_t)ch * 8) * 2);
-    }
+    if (wid < rows) w.each([&](int c, size_t col) { nxt[c] = ld_row8(x, (size_t)wid * ldx + col); });
   }
   for (long row = wid; row < rows; row += nw) {
-    u32x4 v[NCH];
-    float amax = 0.f, ssq = 0.f;
+    u32x4 v[NCH] = {};
+    RowMag m;
+    if constexpr (PF) {
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int ch = lane + c * 64;
-      v[c] = u32x4{0, 0, 0, 0};
-      if constexpr (PF) v[c] = nxt[c];
-      if (ch < nchunks) {
-        if constexpr (PF) { if (row + nw < rows) nxt[c] = ld_stream<u32x4>(x + ((size_t)(row + nw) * ldx + (size_t)ch * 8) * 2); }
-        else v[c] = ld_stream<u32x4>(x + ((size_t)row * ldx + (size_t)ch * 8) * 2);
-        float f[8];
-        unpack8(v[c], f);
+      for (int c = 0; c < NCH; ++c) v[c] = nxt[c];
+    }
+    w.each([&](int c, size_t col) {
+      if constexpr (PF) { if (row + nw < rows) nxt[c] = ld_row8(x, (size_t)(row + nw) * ldx + col); }
+      else v[c] = ld_row8(x, (size_t)row * ldx + col);
+      float f[8];
+      unpack8(v[c], f);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { amax = fmaxf(amax, fabsf(f[i])); cs[c][i] += f[i]; ssq = __builtin_fmaf(f[i], f[i], ssq); }
-      }
-    }
-    amax = wave_max(amax);
-    float s, d;
-    row_scales<FMT>(amax, s, d);
-    if (lane == 0) dq[row] = d;
-    if (rnorm) {      // ||x[row,:]||_2 (engine._row_bound: the Cauchy-Schwarz bound of the input gradient this row produces)
-      const float n2 = wave_sum(ssq);
-      if (lane == 0) rnorm[row] = sqrtf(n2);
-    }
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunks) {
-        float f[8];
-        unpack8(v[c], f);
-        st_stream<u32x2>(q + (size_t)row * ldq + (size_t)ch * 8, cvt8<FMT>(f, s));
-      }
-    }
+      for (int i = 0; i < 8; ++i) cs[c][i] += f[i];
+      m.add8(f);
+    });
+    quantize_row<FMT>(w, v, m, q + (size_t)row * ldq, dq, rnorm, row);
   }
   float* out = partial + (size_t)blockIdx.x * K;
 #pragma unroll
@@ -157,111 +107,34 @@ __global__ __launch_bounds__(256) void colsum_reduce_kernel(const float* __restr
   }
 }
 
-// LayerNorm (transformer.py:19-34) whose output feeds an fp8 GEMM: y = bf16(LN(x)) (optional), q = e4m3(y * s), dq = 1/s
+// LayerNorm (transformer.py:19-34) whose output feeds an fp8 GEMM: y = bf16(LN(x)) (optional), q = e4m3(y * s), dq = 1/s,
+// rnorm = ||y[r,:]||_2 (optional).  The row loop and the statistics are row_wave.h's ln_q8_rows.
 template <int NCH>
 __global__ __launch_bounds__(256) void ln_fwd_q8_kernel(const char* __restrict__ x, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, char* __restrict__ y,
                                                         char* __restrict__ q, float* __restrict__ dq, float* __restrict__ rnorm,
                                                         long rows, int D, float eps) {
-  const int lane = threadIdx.x & 63;
-  const long wid = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const long nw = (long)gridDim.x * 4;
-  const int nchunks = D >> 3;
-  float g[NCH][8], bt[NCH][8];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int ch = lane + c * 64;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { g[c][i] = 0.f; bt[c][i] = 0.f; }
-    if (ch < nchunks) {
-      const float4 a = *(const float4*)(gamma + ch * 8), b = *(const float4*)(gamma + ch * 8 + 4);
-      const float4 e = *(const float4*)(beta + ch * 8), h = *(const float4*)(beta + ch * 8 + 4);
-      g[c][0] = a.x; g[c][1] = a.y; g[c][2] = a.z; g[c][3] = a.w; g[c][4] = b.x; g[c][5] = b.y; g[c][6] = b.z; g[c][7] = b.w;
-      bt[c][0] = e.x; bt[c][1] = e.y; bt[c][2] = e.z; bt[c][3] = e.w; bt[c][4] = h.x; bt[c][5] = h.y; bt[c][6] = h.z; bt[c][7] = h.w;
-    }
-  }
-  const float invD = 1.0f / (float)D;
-  // the next row's loads are issued before this row's arithmetic (LN_Q8_PREFETCH: a wave keeps two rows in flight - these
-  // kernels are latency-bound at one row per wave and ~100 registers, tools/stream8_bench.py)
-  u32x4 nxt[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int ch = lane + c * 64;
-    nxt[c] = u32x4{0, 0, 0, 0};
-    if (ch < nchunks && wid < rows) nxt[c] = ld_stream<u32x4>(x + ((size_t)wid * D + (size_t)ch * 8) * 2);
-  }
-  for (long r = wid; r < rows; r += nw) {
-    float v[NCH][8];
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int ch = lane + c * 64;
-      if (!LN_Q8_PREFETCH && ch < nchunks && r != wid) nxt[c] = ld_stream<u32x4>(x + ((size_t)r * D + (size_t)ch * 8) * 2);
-      unpack8(nxt[c], v[c]);
-      if (ch < nchunks) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) sum += v[c][i];
-        if (LN_Q8_PREFETCH && r + nw < rows) nxt[c] = ld_stream<u32x4>(x + ((size_t)(r + nw) * D + (size_t)ch * 8) * 2);
-      }
-    }
-    const float mean = wave_sum(sum) * invD;
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunks) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const float d = v[c][i] - mean; ss = __builtin_fmaf(d, d, ss); }
-      }
-    }
-    const float rstd = rsqrtf(__builtin_fmaf(wave_sum(ss), invD, eps));      // (layernorm.hip: the expressions of ln_fwd_kernel, fused multiply-adds written out)
-    float amax = 0.f, ssq = 0.f;
-    u32x4 yb[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int ch = lane + c * 64;
-      yb[c] = u32x4{0, 0, 0, 0};
-      if (ch < nchunks) {
-        float o[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = __builtin_fmaf((v[c][i] - mean) * rstd, g[c][i], bt[c][i]);
-        yb[c] = pack8(o);                       // the bf16 rounding of the plain LayerNorm kernel: q is derived from it
-        if (y) st_stream<u32x4>(y + ((size_t)r * D + (size_t)ch * 8) * 2, yb[c]);
-        unpack8(yb[c], o);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { amax = fmaxf(amax, fabsf(o[i])); ssq = __builtin_fmaf(o[i], o[i], ssq); }
-      }
-    }
-    amax = wave_max(amax);
-    float s, d;
-    row_scales<0>(amax, s, d);
-    if (lane == 0) dq[r] = d;
-    if (rnorm) {      // ||y[r,:]||_2: with the next layer's largest weight-row norm a Cauchy-Schwarz bound of that layer's outputs (engine._row_bound)
-      const float n2 = wave_sum(ssq);
-      if (lane == 0) rnorm[r] = sqrtf(n2);
-    }
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunks) {
-        float o[8];
-        unpack8(yb[c], o);
-        st_stream<u32x2>(q + (size_t)r * D + (size_t)ch * 8, cvt8<0>(o, s));
-      }
-    }
-  }
+  ln_q8_rows<NCH>(x, gamma, beta, rows, D, eps, [&](const RowWave<NCH>& w, long r, size_t at, auto&& y8) {
+    u32x4 yb[NCH] = {};
+    RowMag m;
+    w.each([&](int c, size_t col) {
+      float o[8];
+      y8(c, o);
+      yb[c] = pack8(o);                         // the bf16 rounding of the plain LayerNorm kernel: q is derived from it
+      if (y) st_stream(y + (at + col) * 2, yb[c]);
+      unpack8(yb[c], o);
+      m.add8(o);
+    });
+    quantize_row<0>(w, yb, m, q + at, dq, rnorm, r);
+  });
 }
 
 template <int FMT>
 int launch_quant(const void* x, void* q, float* dq, int64_t rows, int64_t K, int64_t ldx, int64_t ldq, hipStream_t st) {
-  const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-  const char* xp = (const char*)x;
-  char* qp = (char*)q;
-  if (K <= 512) hipLaunchKernelGGL((quantize_rows_kernel<1, FMT>), grid, block, 0, st, xp, (long)ldx, qp, (long)ldq, dq, (long)rows, (int)K);
-  else if (K <= 1024) hipLaunchKernelGGL((quantize_rows_kernel<2, FMT>), grid, block, 0, st, xp, (long)ldx, qp, (long)ldq, dq, (long)rows, (int)K);
-  else if (K <= 2048) hipLaunchKernelGGL((quantize_rows_kernel<4, FMT>), grid, block, 0, st, xp, (long)ldx, qp, (long)ldq, dq, (long)rows, (int)K);
-  else if (K <= 4096) hipLaunchKernelGGL((quantize_rows_kernel<8, FMT>), grid, block, 0, st, xp, (long)ldx, qp, (long)ldq, dq, (long)rows, (int)K);
-  else hipLaunchKernelGGL((quantize_rows_kernel<16, FMT>), grid, block, 0, st, xp, (long)ldx, qp, (long)ldq, dq, (long)rows, (int)K);
+  dispatch_nch<1, 2, 4, 8, 16>(K, [&](auto nch) {
+    hipLaunchKernelGGL((quantize_rows_kernel<decltype(nch)::value, FMT>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st,
+                       (const char*)x, (long)ldx, (char*)q, (long)ldq, dq, (long)rows, (int)K);
+  });
   return clipa_check_launch("quantize_rows");
 }
 
@@ -291,19 +164,10 @@ template <int FMT>
 int launch_quant_colsum(const void* x, void* q, float* dq, float* colsum, float* rownorm, float* partial, int64_t rows, int64_t K, int64_t ldx,
                         int64_t ldq, hipStream_t st) {
   const long nb = quant_colsum_blocks(rows);
-  const dim3 grid((unsigned)nb), block(256);
-  const char* xp = (const char*)x;
-  char* qp = (char*)q;
-#define QC_LAUNCH(N) hipLaunchKernelGGL((quantize_rows_colsum_kernel<N, FMT>), grid, block, 0, st, xp, (long)ldx, qp, (long)ldq, dq, partial, rownorm, (long)rows, (int)K)
-  if (K <= 512) QC_LAUNCH(1);
-  else if (K <= 1024) QC_LAUNCH(2);
-  else if (K <= 1536) QC_LAUNCH(3);
-  else if (K <= 2048) QC_LAUNCH(4);
-  else if (K <= 3072) QC_LAUNCH(6);
-  else if (K <= 4096) QC_LAUNCH(8);
-  else if (K <= 5120) QC_LAUNCH(10);
-  else QC_LAUNCH(16);
-#undef QC_LAUNCH
+  dispatch_nch<1, 2, 3, 4, 6, 8, 10, 16>(K, [&](auto nch) {
+    hipLaunchKernelGGL((quantize_rows_colsum_kernel<decltype(nch)::value, FMT>), dim3((unsigned)nb), dim3(256), 0, st,
+                       (const char*)x, (long)ldx, (char*)q, (long)ldq, dq, partial, rownorm, (long)rows, (int)K);
+  });
   if (int rc = clipa_check_launch("quantize_rows_colsum")) return rc;
   hipLaunchKernelGGL(colsum_reduce_kernel, dim3((unsigned)((K + 63) / 64)), dim3(256), 0, st, (const float*)partial, colsum, (int)nb, (int)K);
   return clipa_check_launch("quantize_rows_colsum_reduce");
@@ -335,12 +199,13 @@ extern "C" int clipa_quantize_rows_colsum(const void* x, void* q, float* dq, flo
                   : launch_quant_colsum<1>(x, q, dq, colsum, rownorm, (float*)workspace, rows, K, ldx, ldq, st);
 }
 
-extern "C" int clipa_layernorm_fwd_q8n(const void* x, const float* gamma, const float* beta, void* y, void* q, float* dq,
-                                       float* rownorm, int64_t rows, int64_t D, float eps, void* stream);
-extern "C" int clipa_layernorm_fwd_q8(const void* x, const float* gamma, const float* beta, void* y, void* q, float* dq,
-                                      int64_t rows, int64_t D, float eps, void* stream) {
-  return clipa_layernorm_fwd_q8n(x, gamma, beta, y, q, dq, nullptr, rows, D, eps, stream);
+namespace {
+dim3 ln_q8_grid(int64_t rows) {
+  const long blocks = (rows + 3) / 4;
+  return dim3((unsigned)(blocks > LN_Q8_BLOCK_CAP ? LN_Q8_BLOCK_CAP : blocks));
 }
+}  // namespace
+
 extern "C" int clipa_layernorm_fwd_q8n(const void* x, const float* gamma, const float* beta, void* y, void* q, float* dq,
                                        float* rownorm, int64_t rows, int64_t D, float eps, void* stream) {
   if (rows <= 0) return CLIPA_OK;
@@ -348,16 +213,15 @@ extern "C" int clipa_layernorm_fwd_q8n(const void* x, const float* gamma, const 
   // 8192 blocks striding the rows: at 806 912 x 1024 / 526 336 x 1280 / 157 696 x 1280 the persistent 2048 blocks of rounds
   // 2-3 take 0.827 / 0.733 / 0.221 ms, 8192 blocks 0.679 / 0.706 / 0.218, a one-shot grid 0.722 / 0.862 / 0.256 (gamma and
   // beta are re-read by every wave: 4x the row bytes) - profiles/r04_stream_kernels_old_vs_new_lib.jsonl
-  long blocks = (rows + 3) / 4;
-  if (blocks > LN_Q8_BLOCK_CAP) blocks = LN_Q8_BLOCK_CAP;
-  const dim3 grid((unsigned)blocks), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const char* xp = (const char*)x;
-  if (D <= 512) hipLaunchKernelGGL((ln_fwd_q8_kernel<1>), grid, block, 0, st, xp, gamma, beta, (char*)y, (char*)q, dq, rownorm, (long)rows, (int)D, eps);
-  else if (D <= 1024) hipLaunchKernelGGL((ln_fwd_q8_kernel<2>), grid, block, 0, st, xp, gamma, beta, (char*)y, (char*)q, dq, rownorm, (long)rows, (int)D, eps);
-  else if (D <= 1536) hipLaunchKernelGGL((ln_fwd_q8_kernel<3>), grid, block, 0, st, xp, gamma, beta, (char*)y, (char*)q, dq, rownorm, (long)rows, (int)D, eps);
-  else hipLaunchKernelGGL((ln_fwd_q8_kernel<4>), grid, block, 0, st, xp, gamma, beta, (char*)y, (char*)q, dq, rownorm, (long)rows, (int)D, eps);
+  dispatch_nch<1, 2, 3, 4>(D, [&](auto nch) {
+    hipLaunchKernelGGL((ln_fwd_q8_kernel<decltype(nch)::value>), ln_q8_grid(rows), dim3(256), 0, (hipStream_t)stream,
+                       (const char*)x, gamma, beta, (char*)y, (char*)q, dq, rownorm, (long)rows, (int)D, eps);
+  });
   return clipa_check_launch("layernorm_fwd_q8");
+}
+extern "C" int clipa_layernorm_fwd_q8(const void* x, const float* gamma, const float* beta, void* y, void* q, float* dq,
+                                      int64_t rows, int64_t D, float eps, void* stream) {
+  return clipa_layernorm_fwd_q8n(x, gamma, beta, y, q, dq, nullptr, rows, D, eps, stream);
 }
 
 // ---- operands of the fp8 weight-gradient GEMM (gemm_tn8.hip) --------------------------------------------------------------
@@ -411,72 +275,18 @@ template <int NCH>
 __global__ __launch_bounds__(256) void ln_fwd_q8s_kernel(const char* __restrict__ x, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, const float* __restrict__ rowscale,
                                                          const float* __restrict__ t_dev, char* __restrict__ q, long rows, int D, float eps) {
-  const int lane = threadIdx.x & 63;
-  const long wid = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const long nw = (long)gridDim.x * 4;
-  const int nchunks = D >> 3;
-  float g[NCH][8], bt[NCH][8];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int ch = lane + c * 64;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { g[c][i] = 0.f; bt[c][i] = 0.f; }
-    if (ch < nchunks) {
-      const float4 a = *(const float4*)(gamma + ch * 8), b = *(const float4*)(gamma + ch * 8 + 4);
-      const float4 e = *(const float4*)(beta + ch * 8), h = *(const float4*)(beta + ch * 8 + 4);
-      g[c][0] = a.x; g[c][1] = a.y; g[c][2] = a.z; g[c][3] = a.w; g[c][4] = b.x; g[c][5] = b.y; g[c][6] = b.z; g[c][7] = b.w;
-      bt[c][0] = e.x; bt[c][1] = e.y; bt[c][2] = e.z; bt[c][3] = e.w; bt[c][4] = h.x; bt[c][5] = h.y; bt[c][6] = h.z; bt[c][7] = h.w;
-    }
-  }
-  const float invD = 1.0f / (float)D;
   const float it = inv_or_zero(t_dev[0]);
-  u32x4 nxt[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int ch = lane + c * 64;
-    nxt[c] = u32x4{0, 0, 0, 0};
-    if (ch < nchunks && wid < rows) nxt[c] = ld_stream<u32x4>(x + ((size_t)wid * D + (size_t)ch * 8) * 2);
-  }
-  for (long r = wid; r < rows; r += nw) {
-    float v[NCH][8];
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int ch = lane + c * 64;
-      if (!LN_Q8_PREFETCH && ch < nchunks && r != wid) nxt[c] = ld_stream<u32x4>(x + ((size_t)r * D + (size_t)ch * 8) * 2);
-      unpack8(nxt[c], v[c]);
-      if (ch < nchunks) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) sum += v[c][i];
-        if (LN_Q8_PREFETCH && r + nw < rows) nxt[c] = ld_stream<u32x4>(x + ((size_t)(r + nw) * D + (size_t)ch * 8) * 2);
-      }
-    }
-    const float mean = wave_sum(sum) * invD;
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunks) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const float d = v[c][i] - mean; ss = __builtin_fmaf(d, d, ss); }
-      }
-    }
-    const float rstd = rsqrtf(__builtin_fmaf(wave_sum(ss), invD, eps));      // (layernorm.hip: the expressions of ln_fwd_kernel, fused multiply-adds written out)
+  ln_q8_rows<NCH>(x, gamma, beta, rows, D, eps, [&](const RowWave<NCH>& w, long r, size_t at, auto&& y8) {
     const float s = rowscale[r] * it;
+    w.each([&](int c, size_t col) {
+      float o[8];
+      y8(c, o);
+      unpack8(pack8(o), o);                     // the bf16 rounding of the LayerNorm output the forward GEMM saw
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int ch = lane + c * 64;
-      if (ch < nchunks) {
-        float o[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = __builtin_fmaf((v[c][i] - mean) * rstd, g[c][i], bt[c][i]);
-        unpack8(pack8(o), o);                   // the bf16 rounding of the LayerNorm output the forward GEMM saw
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] *= s;
-        st_stream<u32x2>(q + (size_t)r * D + (size_t)ch * 8, e4m3x8_sat(o));
-      }
-    }
-  }
+      for (int i = 0; i < 8; ++i) o[i] *= s;
+      st_stream(q + at + col, e4m3x8_sat(o));
+    });
+  });
 }
 
 }  // namespace
@@ -652,15 +462,10 @@ extern "C" int clipa_layernorm_fwd_q8s(const void* x, const float* gamma, const 
   if (rows <= 0) return CLIPA_OK;
   if (D <= 0 || D % 8 != 0 || D > 2048) { clipa_set_error("layernorm_fwd_q8s: D=%ld must be a multiple of 8 in (0, 2048]", (long)D); return CLIPA_ERR_ARG; }
   if (!rowscale || !t_dev) { clipa_set_error("layernorm_fwd_q8s: rowscale and t are required"); return CLIPA_ERR_ARG; }
-  long blocks = (rows + 3) / 4;
-  if (blocks > LN_Q8_BLOCK_CAP) blocks = LN_Q8_BLOCK_CAP;
-  const dim3 grid((unsigned)blocks), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const char* xp = (const char*)x;
-  if (D <= 512) hipLaunchKernelGGL((ln_fwd_q8s_kernel<1>), grid, block, 0, st, xp, gamma, beta, rowscale, t_dev, (char*)q, (long)rows, (int)D, eps);
-  else if (D <= 1024) hipLaunchKernelGGL((ln_fwd_q8s_kernel<2>), grid, block, 0, st, xp, gamma, beta, rowscale, t_dev, (char*)q, (long)rows, (int)D, eps);
-  else if (D <= 1536) hipLaunchKernelGGL((ln_fwd_q8s_kernel<3>), grid, block, 0, st, xp, gamma, beta, rowscale, t_dev, (char*)q, (long)rows, (int)D, eps);
-  else hipLaunchKernelGGL((ln_fwd_q8s_kernel<4>), grid, block, 0, st, xp, gamma, beta, rowscale, t_dev, (char*)q, (long)rows, (int)D, eps);
+  dispatch_nch<1, 2, 3, 4>(D, [&](auto nch) {
+    hipLaunchKernelGGL((ln_fwd_q8s_kernel<decltype(nch)::value>), ln_q8_grid(rows), dim3(256), 0, (hipStream_t)stream,
+                       (const char*)x, gamma, beta, rowscale, t_dev, (char*)q, (long)rows, (int)D, eps);
+  });
   return clipa_check_launch("layernorm_fwd_q8s");
 }
 

@@ -72,6 +72,42 @@ def test_quantize_rows(M, K, fmt):
     assert (deq[M // 2] == 0).all() and dq[M // 2].item() == 0.0
 
 
+# K = 512 (NCH - 1) + 8 puts one lane into the last 16-byte chunk of each of quantize_rows_colsum_kernel's eight instantiations
+# (1, 2, 3, 4, 6, 8, 10, 16 chunks per lane) and reaches all five of quantize_rows_kernel (1, 2, 4, 8, 16); 8192 fills the
+# widest.  (8200, 520): more rows than 4 x QUANT_COLSUM_BLOCKS, so the persistent loop and its prefetch run a second pass.
+@pytest.mark.parametrize("fmt", [0, 1])
+@pytest.mark.parametrize("M,K", [(37, K) for K in (8, 520, 1032, 1544, 2568, 3592, 4616, 7688, 8192)] + [(8200, 520)])
+def test_quantize_rows_every_instantiation(M, K, fmt):
+    """Both row quantisers at every compiled chunk count.  Plain form against cpu_quantize and the input (the error bound
+    fails any wrong byte); column-sum form: q, dq equal to the plain form's (same maximum, scale and conversion, only the
+    row-to-wave mapping differs), column sums against fp64 within 1e-5 x the largest column's sum of magnitudes, row norms
+    against the fp32 norms of the input, and a second call returning identical tensors (fixed-order reductions)."""
+    g = torch.Generator().manual_seed(M + K)
+    x = torch.randn(M, K, generator=g) * torch.exp(torch.randn(M, 1, generator=g) * 3.0)   # row magnitudes over ~5 decades
+    x[M // 2] = 0.0                                                                          # an all-zero row (padding tokens)
+    x = x.to(bf16)
+    xd = x.to(DEV)
+    q, dq = ops().quantize_rows(xd, fmt)
+    _, dqr = cpu_quantize(x, fmt)
+    got = q.cpu().view(F8[fmt][0]).float()
+    assert torch.isfinite(got).all()
+    torch.testing.assert_close(dq.cpu(), dqr, rtol=1e-6, atol=0)
+    half_ulp = 2.0 ** -4 if fmt == 0 else 2.0 ** -3
+    deq = got * dq.cpu()[:, None]
+    sub = dq.cpu()[:, None] * (2.0 ** -10 if fmt == 0 else 2.0 ** -17)                  # half a subnormal step
+    assert ((deq - x.float()).abs() <= half_ulp * x.float().abs() * 1.001 + sub).all(), "quantisation error above half an ulp"
+    assert (q[M // 2] == 0).all() and dq[M // 2].item() == 0.0
+
+    qc, dqc, cs, rn = ops().quantize_rows(xd, fmt, want_colsum=True, want_rownorm=True)
+    assert torch.equal(qc, q) and torch.equal(dqc, dq)
+    want = x.double().sum(0)
+    scale = float(x.double().abs().sum(0).max())
+    assert float((cs.cpu().double() - want).abs().max()) <= 1e-5 * scale
+    torch.testing.assert_close(rn.cpu(), x.float().norm(dim=1), rtol=1e-5, atol=1e-6)
+    again = ops().quantize_rows(xd, fmt, want_colsum=True, want_rownorm=True)
+    assert all(torch.equal(a, b) for a, b in zip((qc, dqc, cs, rn), again))
+
+
 def _f8_operands(M, N, K, fmt_a, fmt_b, seed):
     a = rnd(M, K, seed=seed) * torch.exp(rnd(M, 1, seed=seed + 1, dtype=f32))            # asymmetric, row-dependent scales
     b = rnd(N, K, seed=seed + 2, scale=0.05)
