@@ -9,7 +9,9 @@ linear probe (`fewshot_lsr`, `fewshot_metrics`, `evaluate_fewshot`) and fused fp
 (`build_classifier`, `class_mean_embeddings`, `zero_shot_ranks`, `zero_shot_counts`, `zero_shot_metrics`, `evaluate_zero_shot`)
 and top-k similarity search (`topk_similarity`, `classify_topk`, `zero_shot_predict`, `retrieve_topk`, `knn_classify`,
 `knn_metrics`) and the logistic-regression linear probe of Radford et al. 2021 (`fit_logreg`, `logreg_objective`,
-`sweep_l2`, `evaluate_linear_probe`, and `linear_probe.linear_probe` in the module of that name).
+`sweep_l2`, `evaluate_linear_probe`, and `linear_probe.linear_probe` in the module of that name); the device-side input
+pipeline (`DeviceAugment`, `DeviceEvalTransform`, `DevicePrefetcher`) over batches of images of mixed sizes (`RaggedImages`,
+`pack_images`, `ragged_collate`, `eval_geometry`).
 """
 from .configs import add_model_config, get_model_config, list_models
 from .factory import (create_loss, create_model, create_model_and_transforms, get_cast_dtype, load_checkpoint)
@@ -17,7 +19,8 @@ from .loss import ClipLoss, DistillClipLoss, SigLipLoss
 from .model import (CLIP, CLIPTextCfg, CLIPVisionCfg, OPENAI_DATASET_MEAN, OPENAI_DATASET_STD, convert_weights_to_lp,
                     get_2d_sincos_pos_embed, resize_pos_embed, resize_text_pos_embed)
 
-from .data import DeviceAugment, DevicePrefetcher
+from .data import (DeviceAugment, DeviceEvalTransform, DevicePrefetcher, RaggedImages, eval_geometry, pack_images,
+                   ragged_collate)
 from . import fewshot
 from .evaluate import evaluate, get_clip_metrics, metrics_from_ranks
 from .fewshot import evaluate_fewshot, fewshot_lsr, fewshot_metrics

@@ -96,6 +96,183 @@ def sample_crop_boxes(batch, height, width, scale=(0.9, 1.0), ratio=(3.0 / 4.0, 
     return torch.stack([top, left, h, w], 1).to(torch.int32).contiguous()
 
 
+def sample_crop_boxes_ragged(heights, widths, scale=(0.9, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), generator=None):
+    """sample_crop_boxes for images of different sizes: heights, widths [B] -> int32 [B, 4] = (top, left, h, w), each box inside
+    its own image.  The generator is consumed in the same order, so for equal sizes the boxes are those of sample_crop_boxes
+    from the same generator state; the fallback of a sample none of whose ten attempts fits is its own largest central crop
+    inside the ratio bounds (random_resized_crop_params past its loop, computed here without drawing anything)."""
+    height = torch.as_tensor(heights).cpu().long().reshape(-1)
+    width = torch.as_tensor(widths).cpu().long().reshape(-1)
+    batch = height.numel()
+    area = (height * width).double().unsqueeze(1)
+    u = torch.rand(batch, 10, generator=generator, dtype=torch.float64)
+    v = torch.rand(batch, 10, generator=generator, dtype=torch.float64)
+    target = area * (scale[0] + (scale[1] - scale[0]) * u)
+    aspect = torch.exp(math.log(ratio[0]) + (math.log(ratio[1]) - math.log(ratio[0])) * v)
+    w = torch.round(torch.sqrt(target * aspect)).long()
+    h = torch.round(torch.sqrt(target / aspect)).long()
+    ok = (w > 0) & (w <= width.unsqueeze(1)) & (h > 0) & (h <= height.unsqueeze(1))
+    first = torch.where(ok.any(1), ok.float().argmax(1), torch.zeros(batch, dtype=torch.long))
+    idx = torch.arange(batch)
+    w, h = w[idx, first], h[idx, first]
+    in_ratio = width.double() / height.double()
+    narrow, wide = in_ratio < min(ratio), in_ratio > max(ratio)
+    fh = torch.where(narrow, torch.round(width.double() / min(ratio)).long(), height)
+    fw = torch.where(wide & ~narrow, torch.round(height.double() * max(ratio)).long(), width)
+    fi = torch.div(height - fh, 2, rounding_mode="floor")
+    fj = torch.div(width - fw, 2, rounding_mode="floor")
+    none = ~ok.any(1)
+    w, h = torch.where(none, fw, w), torch.where(none, fh, h)
+    ri = torch.rand(batch, generator=generator, dtype=torch.float64)
+    rj = torch.rand(batch, generator=generator, dtype=torch.float64)
+    top = torch.minimum((ri * (height - h + 1).double()).long(), height - h)
+    left = torch.minimum((rj * (width - w + 1).double()).long(), width - w)
+    top, left = torch.where(none, fi, top), torch.where(none, fj, left)
+    return torch.stack([top, left, h, w], 1).to(torch.int32).contiguous()
+
+
+# ---- batches of images of different sizes ---------------------------------------------------------------------------------
+# Decoded dataset images differ in size from sample to sample; resizing them to a common staging size on the host would be the
+# per-sample CPU work this pipeline removes (and a second resample of the pixels).  A batch travels as ONE packed byte buffer
+# plus a size table, and clipa_amd/csrc/resample_ragged.hip resamples every image from its own geometry.
+class RaggedImages:
+    """A batch of H_b x W_b x 3 uint8 images in one buffer: data uint8 [bytes], offsets int64 [B] (byte offset of image b),
+    sizes int32 [B, 2] = (H_b, W_b).  The two tables also stay on the host (host_tables), where the launch geometry is derived."""
+
+    def __init__(self, data, offsets, sizes, host=None):
+        self.data, self.offsets, self.sizes = data, offsets, sizes
+        if data.dim() != 1 or data.dtype != torch.uint8 or offsets.dtype != torch.int64 or sizes.dtype != torch.int32:
+            raise ValueError("RaggedImages: data uint8 [bytes], offsets int64 [B], sizes int32 [B,2]")
+        if sizes.dim() != 2 or sizes.shape[1] != 2 or offsets.shape != sizes.shape[:1]:
+            raise ValueError(f"RaggedImages: offsets [B] and sizes [B,2], got {tuple(offsets.shape)} and {tuple(sizes.shape)}")
+        self._host = host
+
+    def __len__(self):
+        return self.offsets.numel()
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def host_tables(self):
+        """-> (offsets, sizes) on the CPU (copied back once if this batch was built from device tensors)."""
+        if self._host is None:
+            self._host = (self.offsets.cpu(), self.sizes.cpu())
+        return self._host
+
+    def to(self, device, non_blocking=False):
+        host = self.host_tables()
+        put = lambda t: t.to(device, non_blocking=non_blocking)
+        return RaggedImages(put(self.data), put(self.offsets), put(self.sizes), host)
+
+    def pin_memory(self):
+        return RaggedImages(self.data.pin_memory(), self.offsets.pin_memory(), self.sizes.pin_memory(), self._host)
+
+    def is_pinned(self):
+        return self.data.is_pinned() and self.offsets.is_pinned() and self.sizes.is_pinned()
+
+    def record_stream(self, stream):
+        for t in (self.data, self.offsets, self.sizes):
+            t.record_stream(stream)
+
+    def image(self, i):
+        """Image i as an [H, W, 3] view of the buffer."""
+        offsets, sizes = self.host_tables()
+        o, h, w = int(offsets[i]), int(sizes[i, 0]), int(sizes[i, 1])
+        return self.data[o:o + h * w * 3].view(h, w, 3)
+
+    @staticmethod
+    def from_uniform(batch):
+        """A contiguous uint8 [B, H, W, 3] tensor as a ragged batch of equal sizes (a view: no pixel is copied)."""
+        if batch.dim() != 4 or batch.shape[3] != 3 or batch.dtype != torch.uint8:
+            raise ValueError(f"RaggedImages.from_uniform: uint8 [B,H,W,3], got {batch.dtype} {tuple(batch.shape)}")
+        B, H, W, _ = batch.shape
+        offsets = torch.arange(B, dtype=torch.int64) * (H * W * 3)
+        sizes = torch.tensor([[H, W]], dtype=torch.int32).repeat(B, 1)
+        put = (lambda t: t.pin_memory().to(batch.device, non_blocking=True)) if batch.is_cuda else (lambda t: t)
+        return RaggedImages(batch.contiguous().view(-1), put(offsets), put(sizes), (offsets, sizes))
+
+
+RAGGED_ALIGN = 16      # every image of a packed batch starts at a multiple of this many bytes
+
+
+def _image_tables(images):
+    """Sizes and aligned offsets of a list of uint8 [H, W, 3] arrays / tensors -> (tensors, offsets, sizes, total bytes)."""
+    tensors = []
+    for i, im in enumerate(images):
+        t = torch.as_tensor(im)
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"pack_images: image {i} must be a uint8 [H, W, 3] array, got {t.dtype} {tuple(t.shape)}")
+        tensors.append(t)
+    sizes = torch.tensor([[t.shape[0], t.shape[1]] for t in tensors], dtype=torch.int32).reshape(-1, 2)
+    nbytes = (sizes[:, 0].long() * sizes[:, 1].long() * 3 + RAGGED_ALIGN - 1) // RAGGED_ALIGN * RAGGED_ALIGN
+    offsets = torch.cumsum(nbytes, 0) - nbytes
+    return tensors, offsets, sizes, int(nbytes.sum())
+
+
+def _fill_packed(data, tensors, offsets):
+    for t, o in zip(tensors, offsets.tolist()):
+        data[o:o + t.numel()].view(t.shape).copy_(t)
+    return data
+
+
+def pack_images(images, pinned=False):
+    """A list of uint8 [H, W, 3] arrays or tensors (decoded images, any sizes) -> RaggedImages on the CPU (in pinned memory if
+    asked); each image starts at a 16-byte aligned offset."""
+    tensors, offsets, sizes, total = _image_tables(images)
+    data = _fill_packed(torch.zeros(total, dtype=torch.uint8, pin_memory=bool(pinned)), tensors, offsets)
+    return RaggedImages(data, offsets, sizes, (offsets, sizes))
+
+
+def ragged_collate(samples):
+    """collate_fn for datasets whose samples are (uint8 [H, W, 3] image, rest...): -> (RaggedImages, default_collate(rest))."""
+    from torch.utils.data import default_collate
+    rest = [s[1] if len(s) == 2 else tuple(s[1:]) for s in samples]
+    return pack_images([s[0] for s in samples]), default_collate(rest)
+
+
+def eval_geometry(sizes, image_size, square_resize_only=False):
+    """The geometry of the inference transform (open_clip/transform.py:186-213) for images of sizes int [B, 2] = (H, W): int32
+    [B, 8] = (box top, left, height, width, out_h, out_w, oy, ox) as ops.resample_ragged_u8 takes it.  The box is the whole image.
+    Resize(S) + CenterCrop(S): the short side becomes S and the long side int(S * long / short) (the image is left as it is when
+    its short side already is S), the window starts at int(round((out - S) / 2.)) - Python's round, half to even.  The long
+    side is >= S after Resize(S), so CenterCrop's padding branch never occurs.  square_resize_only: Resize((S, S)), window (0, 0)."""
+    S = int(image_size)
+    hw = torch.as_tensor(sizes).cpu().long().reshape(-1, 2)
+    H, W = hw[:, 0], hw[:, 1]
+    zero = torch.zeros_like(H)
+    if square_resize_only:
+        oh = ow = torch.full_like(H, S)
+        oy = ox = zero
+    else:
+        short, long = torch.minimum(H, W), torch.maximum(H, W)
+        new_long = torch.where(short == S, long, ((S * long).double() / short.double()).long())
+        oh = torch.where(W <= H, new_long, torch.full_like(H, S))
+        ow = torch.where(W <= H, torch.full_like(H, S), new_long)
+        oy = torch.round((oh - S).double() / 2.0).long()
+        ox = torch.round((ow - S).double() / 2.0).long()
+    return torch.stack([zero, zero, H, W, oh, ow, oy, ox], 1).to(torch.int32).contiguous()
+
+
+class DeviceEvalTransform:
+    """The reference's inference transform up to PILToTensor (image_transform(is_train=False), open_clip/transform.py:186-213:
+    Resize(S, interpolation) + CenterCrop(S), or Resize((S, S)) with square_resize_only) on a device batch: a RaggedImages, or a
+    uniform uint8 [B, H, W, 3] tensor (taken as a ragged batch of equal sizes).  Returns uint8 [B, 3, S, S] in channels_last
+    memory - the model's input format; mean / std are applied by the patch gather."""
+
+    def __init__(self, image_size, interpolation="bicubic", square_resize_only=False):
+        if interpolation not in ("bicubic", "bilinear"):
+            raise ValueError(f"DeviceEvalTransform: interpolation must be 'bicubic' or 'bilinear', got {interpolation!r}")
+        self.size, self.interpolation, self.square = int(image_size), interpolation, bool(square_resize_only)
+
+    def __call__(self, images):
+        from . import ops
+        if not isinstance(images, RaggedImages):
+            images = RaggedImages.from_uniform(images)
+        geometry = eval_geometry(images.host_tables()[1], self.size, self.square)
+        return ops.resample_ragged_u8(images, geometry, self.size, self.interpolation).permute(0, 3, 1, 2)
+
+
 def sample_color_jitter(batch, brightness, contrast, saturation, hue, prob, generator=None):
     """Per-sample parameters of `color_jitter(brightness, contrast, saturation, hue, p)` (open_clip/transform.py:61-72 around
     torchvision ColorJitter.get_params): apply ~ Bernoulli(prob) uint8 [B], a random permutation of the four operations
@@ -113,7 +290,8 @@ class DeviceAugment:
     """The reference's train transform (open_clip/transform.py:152-168) on a staged uint8 NHWC device batch:
     RandomResizedCrop(image_size, scale, ratio, BICUBIC) -> [color_jitter(b, c, s, h) with probability color_jitter_prob] ->
     [gray_scale with probability gray_scale_prob].  Returns uint8 [B, 3, S, S] in channels_last memory - the model's input
-    format.  Random parameters are sampled on the host (a few bytes per sample); the pixels never leave the device."""
+    format.  Random parameters are sampled on the host (a few bytes per sample); the pixels never leave the device.
+    A RaggedImages batch (images of different sizes) is taken as well: every crop box is sampled inside its own image."""
 
     def __init__(self, image_size, scale=(0.9, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), color_jitter=None, color_jitter_prob=0.0,
                  gray_scale_prob=0.0, seed=0):
@@ -126,22 +304,35 @@ class DeviceAugment:
         self.gen = torch.Generator(device="cpu").manual_seed(int(seed))
 
     def sample(self, B, Hs, Ws):
-        """-> boxes int32 [B,4], (apply, order, factors) | None, gray uint8 [B] | None: one batch's random parameters (CPU)."""
-        boxes = sample_crop_boxes(B, Hs, Ws, self.scale, self.ratio, self.gen)
+        """-> boxes int32 [B,4], (apply, order, factors) | None, gray uint8 [B] | None: one batch's random parameters (CPU).
+        Hs, Ws: the staged size, or per-sample heights and widths [B] of a ragged batch (the same random stream)."""
+        if torch.is_tensor(Hs) or isinstance(Hs, (list, tuple)):
+            boxes = sample_crop_boxes_ragged(Hs, Ws, self.scale, self.ratio, self.gen)
+        else:
+            boxes = sample_crop_boxes(B, Hs, Ws, self.scale, self.ratio, self.gen)
         jit = sample_color_jitter(B, *self.jitter, self.jitter_p, self.gen) if self.jitter_p > 0 else None
         gray = (torch.rand(B, generator=self.gen) < self.gray_p).to(torch.uint8) if self.gray_p > 0 else None
         return boxes, jit, gray
 
     def __call__(self, staged):
         from . import ops
-        B, Hs, Ws, _ = staged.shape
-        boxes, jit, gray = self.sample(B, Hs, Ws)
-        put = (lambda t: t.pin_memory().to(staged.device, non_blocking=True)) if staged.is_cuda else (lambda t: t)
-        boxes = put(boxes)
+        ragged = isinstance(staged, RaggedImages)
+        on_gpu = (staged.data if ragged else staged).is_cuda
+        put = (lambda t: t.pin_memory().to(staged.device, non_blocking=True)) if on_gpu else (lambda t: t)
+        if ragged:                            # images of different sizes: every box is sampled inside its own image
+            B, sizes = len(staged), staged.host_tables()[1]
+            boxes, jit, gray = self.sample(B, sizes[:, 0], sizes[:, 1])
+            geometry = torch.cat([boxes, torch.tensor([[self.size, self.size, 0, 0]], dtype=torch.int32).repeat(B, 1)], 1)
+            resize = lambda flags: ops.resample_ragged_u8(staged, geometry, self.size, "bicubic", flags)
+        else:
+            B, Hs, Ws, _ = staged.shape
+            boxes, jit, gray = self.sample(B, Hs, Ws)
+            boxes = put(boxes)
+            resize = lambda flags: ops.resized_crop_u8(staged, boxes, self.size, flags)
         gray = put(gray) if gray is not None else None
         if jit is None:                       # grayscale rides in the resize kernel's store
-            return ops.resized_crop_u8(staged, boxes, self.size, gray).permute(0, 3, 1, 2)
-        out = ops.resized_crop_u8(staged, boxes, self.size)
+            return resize(gray).permute(0, 3, 1, 2)
+        out = resize(None)
         apply, order, factors = (put(t) for t in jit)
         ops.color_jitter_u8_(out, apply, order, factors, gray)
         return out.permute(0, 3, 1, 2)
@@ -150,7 +341,10 @@ class DeviceAugment:
 class DevicePrefetcher:
     """Iterate a host loader of (images uint8 [B,H,W,3] or [B,3,H,W], texts int64 [B,ctx]) batches `depth` batches ahead:
     each batch is staged in a pinned buffer, copied on a dedicated HIP stream and (optionally) augmented there, so the H2D
-    copy of training/train.py:187-189 and the transform overlap the previous step instead of preceding this one."""
+    copy of training/train.py:187-189 and the transform overlap the previous step instead of preceding this one.
+    The first element may also be a batch of images of different sizes - a RaggedImages (ragged_collate) or a list of uint8
+    [H, W, 3] arrays - for a transform that takes one (DeviceEvalTransform, DeviceAugment); the second may be any tensor
+    (labels, ids), so the output feeds the evaluators as a loader of (images, ...) batches."""
 
     def __init__(self, loader, device, transform=None, depth=2):
         self.loader, self.device, self.transform, self.depth = loader, torch.device(device), transform, max(1, int(depth))
@@ -170,11 +364,44 @@ class DevicePrefetcher:
         buf.copy_(t)
         return buf
 
+    def _grown(self, slot, name, numel, dtype):
+        """A pinned 1-D buffer of this slot with room for numel elements: kept, and replaced only by a larger one."""
+        buf = self._pins[slot].get(name)
+        if buf is None or buf.numel() < numel or buf.dtype != dtype:
+            buf = torch.empty(max(int(numel), 1), dtype=dtype, pin_memory=True)
+            self._pins[slot][name] = buf
+        return buf
+
+    def _stage_ragged(self, slot, images):
+        """Images of different sizes - a RaggedImages or a list of uint8 [H, W, 3] arrays - in this slot's pinned buffers, which
+        grow to the largest batch seen."""
+        if not self.cuda:
+            return images if isinstance(images, RaggedImages) else pack_images(images)
+        if isinstance(images, RaggedImages):
+            if images.is_pinned():
+                return images
+            data = self._grown(slot, "ragged", images.data.numel(), torch.uint8)[:images.data.numel()]
+            data.copy_(images.data)
+            offsets, sizes = images.host_tables()
+        else:
+            tensors, offsets, sizes, total = _image_tables(images)
+            data = _fill_packed(self._grown(slot, "ragged", total, torch.uint8)[:total], tensors, offsets)
+        B = offsets.numel()
+        p_off = self._grown(slot, "ragged_offsets", B, torch.int64)[:B]
+        p_size = self._grown(slot, "ragged_sizes", 2 * B, torch.int32)[:2 * B].view(B, 2)
+        p_off.copy_(offsets)
+        p_size.copy_(sizes)
+        return RaggedImages(data, p_off, p_size, (offsets, sizes))
+
     def _submit(self, slot, batch):
         images, texts = batch
         if self._free[slot] is not None:
             self._free[slot].synchronize()                     # the copy that last read this slot's pinned buffers is done
-        images, texts = self._stage(slot, "images", images), self._stage(slot, "texts", texts)
+        if isinstance(images, (RaggedImages, list, tuple)):
+            images = self._stage_ragged(slot, images)
+        else:
+            images = self._stage(slot, "images", images)
+        texts = self._stage(slot, "texts", texts)
         if not self.cuda:
             return (self.transform(images) if self.transform else images), texts, None
         with torch.cuda.stream(self.stream):

@@ -39,6 +39,8 @@ SIGNATURES = {
     "clipa_resized_crop_workspace": (_I64, [_I64, _I64, _I64]),
     "clipa_resized_crop_u8": (_I32, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _I64, _P, _P]),
     "clipa_color_jitter_u8": (_I32, [_P, _P, _P, _P, _P, _I64, _I64, _P, _I64, _P]),
+    "clipa_resample_ragged_workspace": (_I64, [_I64, _I64, _I64, _I64]),
+    "clipa_resample_ragged_u8": (_I32, [_P, _I64, _P, _P, _P, _I64, _I64, _I32, _I64, _I64, _I64, _P, _I64, _P, _P]),
     "clipa_assemble_tokens": (_I32, [_P, _P, _P, _P, _I64, _I64, _I64, _P]),
     "clipa_assemble_tokens_bwd_workspace": (_I64, [_I64, _I64, _I64]),
     "clipa_assemble_tokens_bwd": (_I32, [_P, _P, _P, _P, _I64, _I64, _I64, _P, _I64, _P]),

@@ -716,6 +716,102 @@ def resized_crop_u8(src, boxes, size, gray_flags=None):
     return out
 
 
+RAGGED_MAX_SIDE, RAGGED_MAX_DOWN, RAGGED_MAX_SIZE = 16384, 64, 4096      # csrc/resample_ragged.hip: RR_MAX_SIDE, RR_MAX_DOWN
+_RAGGED_FILTERS = {"bicubic": (0, 2.0), "bilinear": (1, 1.0)}             # name -> (filter id of the C entry, Pillow's support)
+
+
+def _ragged_refuse(bad, what):
+    """ValueError naming the first sample of the bool [B] mask `bad`."""
+    if bool(bad.any()):
+        i = int(bad.to(torch.uint8).argmax())
+        raise ValueError(f"resample_ragged_u8: sample {i}: {what}")
+
+
+def ragged_layout(offsets, sizes, geometry, size, interpolation="bicubic", packed_bytes=None, validate=True):
+    """Host side of clipa_resample_ragged_u8: the per-sample descriptors with each sample's own storage, from the size table.
+    offsets int64 [B], sizes int32 [B,2] = (H, W), geometry int32 [B,8] = (box top, left, height, width, out_h, out_w, oy, ox),
+    all on the CPU -> (desc int64 [B,16], max_rows, tmp_bytes, coef_ints, moved bytes).  What the entry refuses is refused
+    here, with the sample's index: a side above 16384 or a down-scale above 64x always; with validate, also a descriptor the
+    device would reject (image outside the packed buffer, box outside the image, window outside the resized image)."""
+    if interpolation not in _RAGGED_FILTERS:
+        raise ValueError(f"resample_ragged_u8: interpolation must be 'bicubic' or 'bilinear', got {interpolation!r}")
+    S = int(size)
+    if not 1 <= S <= RAGGED_MAX_SIZE:
+        raise ValueError(f"resample_ragged_u8: size must be in 1..{RAGGED_MAX_SIZE}, got {size}")
+    off, hw, g = offsets.to(torch.int64), sizes.to(torch.int64), geometry.to(torch.int64)
+    B = off.numel()
+    if tuple(hw.shape) != (B, 2) or tuple(g.shape) != (B, 8):
+        raise ValueError(f"resample_ragged_u8: sizes must be [{B},2] and geometry [{B},8], got {tuple(hw.shape)} and {tuple(g.shape)}")
+    H, W = hw[:, 0], hw[:, 1]
+    top, left, bh, bw, oh, ow, oy, ox = g.unbind(1)
+    sides = torch.stack([H, W, bh, bw, oh, ow], 1)
+    _ragged_refuse(((sides < 1) | (sides > RAGGED_MAX_SIDE)).any(1), f"image, box and resized sides must be in 1..{RAGGED_MAX_SIDE}")
+    _ragged_refuse((bh > oh * RAGGED_MAX_DOWN) | (bw > ow * RAGGED_MAX_DOWN), f"down-scale above {RAGGED_MAX_DOWN}x")
+    if validate:
+        bad = off < 0
+        if packed_bytes is not None:
+            bad |= off + H * W * 3 > int(packed_bytes)
+        _ragged_refuse(bad, "image outside the packed buffer")
+        _ragged_refuse((top < 0) | (left < 0) | (top + bh > H) | (left + bw > W), "crop box outside the image")
+        _ragged_refuse((oy < 0) | (ox < 0) | (oy + S > oh) | (ox + S > ow), f"the {S} x {S} window lies outside the resized image")
+    support = _RAGGED_FILTERS[interpolation][1]
+
+    def taps(n_in, n_out):          # Resample.c precompute_coeffs: ksize, in the same double operations
+        scale = n_in.double() / n_out.double()
+        sup = support * scale.clamp(min=1.0)
+        return scale, sup, torch.ceil(sup).long() * 2 + 1
+
+    _, _, kh = taps(bw, ow)
+    scale, sup, kv = taps(bh, oh)
+    # the box rows that the window's vertical taps read: xmin of its first row .. xmax of its last (C casts truncate)
+    first = ((oy.double() + 0.5) * scale - sup + 0.5).long().clamp(min=0)
+    last = torch.minimum((((oy + S - 1).double() + 0.5) * scale + sup + 0.5).long(), bh)
+    rows = torch.minimum((last - first).clamp(min=1), bh)
+    tmp = (rows * S * 3 + 15) // 16 * 16
+    coef = S * (kh + kv)
+    tmp_off, coef_off = torch.cumsum(tmp, 0) - tmp, torch.cumsum(coef, 0) - coef
+    desc = torch.stack([off, H, W, top, left, bh, bw, oh, ow, oy, ox, tmp_off, coef_off, kh, kv, rows], 1).contiguous()
+    nbytes = 3.0 * float((rows * (bw + 2 * S)).sum() + B * S * S)
+    return desc, int(rows.max()) if B else 1, int(tmp.sum()), int(coef.sum()), nbytes
+
+
+def resample_ragged_u8(images, geometry, size, interpolation="bicubic", gray_flags=None, validate=True):
+    """Device-side resize of a batch of images of DIFFERENT sizes (+ Grayscale of the flagged samples), bit-exact with Pillow:
+    out[b] = resize(crop(image b, box b), (out_h, out_w), interpolation)[oy : oy + size, ox : ox + size] -> uint8 [B,size,size,3].
+    images: a clipa_amd.data.RaggedImages on the device; geometry int32 [B,8] = (box top, left, height, width, out_h, out_w,
+    oy, ox) on the CPU - data.eval_geometry for the inference transform, a sampled box with (size, size, 0, 0) for
+    RandomResizedCrop.  A side above 16384, a down-scale above 64x or (validate) a descriptor that leaves its image raise a
+    ValueError that names the sample; validate=False leaves the latter to the device, where such samples come back as zeros and
+    raise at the next check."""
+    data = images.data
+    _chk(data, u8, "images.data", 1)
+    if not data.is_contiguous():
+        raise RuntimeError("resample_ragged_u8: images.data must be a contiguous 1-D uint8 tensor")
+    offsets, sizes = images.host_tables()
+    B = offsets.numel()
+    geometry = torch.as_tensor(geometry).cpu()
+    if gray_flags is not None:
+        _chk(gray_flags, u8, "gray_flags", 1)
+        if gray_flags.numel() != B:
+            raise RuntimeError("resample_ragged_u8: gray_flags must have one byte per sample")
+    if B > 65535:
+        raise ValueError(f"resample_ragged_u8: at most 65535 samples per call, got {B}")
+    desc, max_rows, tmp_bytes, coef_ints, nbytes = ragged_layout(offsets, sizes, geometry, size, interpolation, data.numel(), validate)
+    size = int(size)
+    check_token_ids()                                   # surfaces an earlier launch's rejected samples
+    out = torch.empty((B, size, size, 3), device=data.device, dtype=u8)
+    if B == 0:
+        return out
+    desc = desc.pin_memory().to(data.device, non_blocking=True)
+    ws, wsb = _workspace("clipa_resample_ragged_workspace", B, size, tmp_bytes, coef_ints, device=data.device, dtype=u8, floor=0)
+    err = _oob_counter(data.device)
+    with _Timed("resample_ragged", 0.0, nbytes):
+        lib.call("clipa_resample_ragged_u8", _p(data), data.numel(), _p(desc), _p(gray_flags), _p(out), B, size,
+                 _RAGGED_FILTERS[interpolation][0], max_rows, tmp_bytes, coef_ints, _p(ws), wsb, _p(err), _stream())
+    _oob_submit(err, "resample_ragged_u8", "samples rejected (image, crop box or window outside its bounds, or a down-scale above 64x)")
+    return out
+
+
 def color_jitter_u8_(img, apply=None, order=None, factors=None, gray_flags=None):
     """In place on uint8 [B,S,S,3]: torchvision ColorJitter with per-sample op order (int32 [B,4] over 0 brightness, 1 contrast,
     2 saturation, 3 hue) and factors (f32 [B,4], indexed by op) for the samples with apply[b] != 0, then Grayscale(3) of the

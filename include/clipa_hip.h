@@ -218,6 +218,24 @@ int clipa_resized_crop_u8(const void* src, const int32_t* boxes, const uint8_t* 
  * 160-168, bit-exact with the Pillow code they run on PIL images.  workspace: 8 bytes per sample. */
 int clipa_color_jitter_u8(void* img, const uint8_t* apply, const int32_t* order, const float* factors, const uint8_t* gray_flags,
                           int64_t B, int64_t S, void* workspace, int64_t workspace_bytes, void* stream);
+/* The same resampler on a RAGGED batch - every sample its own source size - and with the inference geometry: replaces the
+ * per-sample CPU work of the train transform (open_clip/transform.py:152-168) for images of mixed sizes and of the eval
+ * transform, Resize(S, bicubic | bilinear) + CenterCrop(S) or Resize((S, S)) (open_clip/transform.py:186-213; --interpolation,
+ * --square-resize-only of training/params.py:445-454):
+ *   out[b][y][x] = Grayscale?(resize(crop(img_b, box_b), (out_h_b, out_w_b), filter))[oy_b + y][ox_b + x],  0 <= y, x < S
+ * bit-exact with Pillow's ImagingResample.  img_b is H_b x W_b x 3 uint8 at byte offset off_b of `packed` (packed_bytes long);
+ * out is uint8 [B,S,S,3]; filter 0 bicubic, 1 bilinear.  desc is int64 [B][16] on the device: off, H, W, box top, left,
+ * height, width, out_h, out_w, oy, ox, then the sample's storage, laid out by the host from the size table: byte offset of its
+ * intermediate rows in the tmp_bytes region, int offset of its coefficient tables in the coef_ints region (S x kh horizontal,
+ * then S x kv vertical), kh, kv (taps per output coordinate, >= 2 * ceil(support * max(1, in / out)) + 1) and the number of
+ * intermediate rows reserved; max_rows = the largest such number.  Every descriptor is validated on the device before it is
+ * dereferenced (image inside [packed, packed + packed_bytes), box inside the image, window inside the resized image, sides
+ * <= 16384, down-scale <= 64x per axis, storage inside the workspace): a failing sample is counted in err_count (device
+ * int32, may be NULL) and its output is zeros. */
+int64_t clipa_resample_ragged_workspace(int64_t B, int64_t S, int64_t tmp_bytes, int64_t coef_ints);
+int clipa_resample_ragged_u8(const void* packed, int64_t packed_bytes, const int64_t* desc, const uint8_t* gray_flags, void* out,
+                             int64_t B, int64_t S, int filter, int64_t max_rows, int64_t tmp_bytes, int64_t coef_ints,
+                             void* workspace, int64_t workspace_bytes, int32_t* err_count, void* stream);
 /* cat(class_embedding) + positional_embedding (transformer.py:496-499) and its gradient. */
 int clipa_assemble_tokens(const void* patch, const float* cls, const float* pos, void* tokens, int64_t B,
                           int64_t L, int64_t D, void* stream);
