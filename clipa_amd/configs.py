@@ -38,6 +38,9 @@ def _builtin():
         for patch in (32, 16, 14):
             cfgs[f"ViT-{size}-{patch}"] = _vit(size, patch)
     cfgs["ViT-B-16-CL16"] = _vit("B", 16, ctx=16)
+    # the B/16 tower with the JAX model's multihead attention pooling head (clipa_jax/models/vit.py:187-207), as SigLIP trains it
+    cfgs["ViT-B-16-MAP-BigVision"] = _vit("B", 16)
+    cfgs["ViT-B-16-MAP-BigVision"]["vision_cfg"].update(pool_style="big_vision_map", gelu_approximate="tanh")
     for ctx in (8, 16):
         cfgs[f"ViT-L-16-CL{ctx}-Syntax-GAP"] = _vit("L", 16, ctx=ctx, gap=True, text_mask="syntax")
     cfgs["ViT-L-16-CL32-GAP"] = _vit("L", 16, ctx=32, gap=True)

@@ -9,6 +9,7 @@ it stands in for (paths relative to /root/reference/clipa_torch):
   TokenDropFn    PatchDropout (row selection)              open_clip/transformer.py:53-83,501-502
   TextStemFn     token_embedding + positional_embedding    open_clip/model.py:245-247
   HeadFn         pool + ln_post/ln_final + projection      transformer.py:509-529, model.py:251-260
+  MapHeadFn      multihead attention pooling + projection  clipa_jax/models/vit.py:187-207,282-284 (JAX tree)
   L2NormFn       F.normalize(dim=-1)                       open_clip/model.py:240,263
 
 Activation policy: a block keeps only its bf16 input and recomputes the rest in backward (what the
@@ -744,6 +745,118 @@ class HeadFn(torch.autograd.Function):
                 _like_param(d_ln_w, ln_w) if ln_w.requires_grad else None,
                 _like_param(d_ln_b, ln_b) if ln_b.requires_grad else None,
                 d_proj)
+
+
+@dataclasses.dataclass(frozen=True)
+class MapHeadCfg:
+    """MapHeadFn: B samples of L tokens, H heads, the MLP's activation (ops.ACT_*), the LayerNorm's eps."""
+    B: int
+    L: int
+    H: int
+    act: int
+    eps: float
+
+
+def _map_fold(cache, probe, w_in, b_in, H):
+    """The folded query of the MAP head, rebuilt when probe / in_proj_weight / in_proj_bias change: q = probe Wq^T + bq (one
+    query for every sample), Qs[h, j] = dh^-0.5 q[j] for the channels j of head h (zero elsewhere, bf16) and
+    U = Qs Wk ([H, D] bf16): s[b,l,h] = x[b,l,:] . U[h,:].  The bk_h . q_h term of the scores is constant over l and cancels in
+    the softmax: it is never computed.  -> (U, Qs, head mask [H, D] f32)."""
+    def make(pr, w, b):
+        D = w.shape[1]
+        dh = D // H
+        wq, bq = cache.w(w_in)[:D], cache.f32(b_in)[:D]
+        q = ops.gemm_nt(ops.to_bf16(pr.reshape(1, D)), wq, bq, out_f32=True)                     # [1, D] f32
+        mask = (torch.arange(D, device=w.device) // dh == torch.arange(H, device=w.device)[:, None]).to(f32)
+        qs = ops.to_bf16((q * float(dh) ** -0.5).expand(H, D) * mask)
+        u = ops.gemm_nt(qs, cache.wt(w_in)[:, D:2 * D])                                           # [H, D(j)] x [D(d), D(j)]^T
+        return u, qs, mask
+    return cache.multi((probe, w_in, b_in), "map_fold%d" % H, make)
+
+
+class MapHeadFn(torch.autograd.Function):
+    """Multihead attention pooling + projection (clipa_jax/models/vit.py:187-207,282-284; no encoder_norm in front, no ln_post):
+        a = MHA_H(probe Wq^T + bq, x Wk^T + bk, x Wv^T + bv) Wo^T + bo;  out = a + c_proj(act(c_fc(LayerNorm(a))));  feat = out @ proj
+    on the [B*L, D] bf16 output of the tower -> f32 [B, E] like HeadFn.  LayerNorm eps is the engine's 1e-5 (flax's default is
+    1e-6).  The one query is the same for every sample, so the K and V projections fold out of the token-level work (_map_fold;
+    csrc/mappool.hip): z[b,h,:] = sum_l softmax_l(x U_h^T) x[b,l,:] in one read of x, then head_h = Wv_h z[b,h,:] + bv_h (sum_l p
+    = 1) and everything after it on B rows with the engine's GEMM / LayerNorm launches.  Saved for backward: z, the softmax
+    statistics and B-row tensors; the only [B*L]-row tensor the head allocates is dx.  Rounding points beside the kernel's own
+    (P, dS, dz as bf16 MFMA operands): q, U, z and dU are rounded to bf16 where a bf16 GEMM takes them.  d bk = 0 exactly."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, cache, probe, w_in, b_in, w_out, b_out, ln_w, ln_b, w_fc, b_fc, w_proj, b_proj, proj):
+        B, L, H = cfg.B, cfg.L, cfg.H
+        D = x.shape[1]
+        dh = D // H
+        u, _, _ = _map_fold(cache, probe, w_in, b_in, H)
+        z, stats = ops.mappool_fwd(x, u, B, L, H)
+        zb = ops.to_bf16(z)                                                  # [B, H, D]
+        wv, bv = cache.w(w_in)[2 * D:], cache.f32(b_in)[2 * D:]
+        heads = torch.empty((B, D), device=x.device, dtype=bf16)
+        for h in range(H):
+            hs = slice(h * dh, (h + 1) * dh)
+            ops.gemm_nt(zb[:, h], wv[hs], bv[hs], out=heads[:, hs])
+        a = ops.gemm_nt(heads, cache.w(w_out), cache.f32(b_out))
+        y = ops.layernorm_fwd(a, cache.f32(ln_w), cache.f32(ln_b), cfg.eps)
+        g, hpre = ops.gemm_nt(y, cache.w(w_fc), cache.f32(b_fc), epi=ops.EPI_ACT, act=cfg.act, want_pre=True)
+        out = ops.gemm_nt(g, cache.w(w_proj), cache.f32(b_proj), epi=ops.EPI_ADD, aux=a)
+        feat = ops.gemm_nt(out, cache.wt(proj), out_f32=True)
+        ctx.cfg, ctx.cache = cfg, cache
+        ctx.params = (probe, w_in, b_in, w_out, b_out, ln_w, ln_b, w_fc, b_fc, w_proj, b_proj, proj)
+        ctx.save_for_backward(x, z, stats)
+        ctx.rows = (zb, heads, a, y, hpre, g, out)      # the B-row tensors: released in backward before dx is allocated
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        x, z, stats = ctx.saved_tensors
+        (zb, heads, a, y, hpre, g, out), ctx.rows = ctx.rows, None
+        cfg, cache = ctx.cfg, ctx.cache
+        probe, w_in, b_in, w_out, b_out, ln_w, ln_b, w_fc, b_fc, w_proj, b_proj, proj = ctx.params
+        B, L, H = cfg.B, cfg.L, cfg.H
+        D = x.shape[1]
+        dh = D // H
+        u, qs, mask = _map_fold(cache, probe, w_in, b_in, H)
+        # the input-gradient chain on B rows down to dz
+        dfb = ops.to_bf16(dfeat.contiguous())
+        dout = ops.gemm_nt(dfb, cache.w(proj))                               # [B,E] @ proj[D,E]^T -> [B,D]
+        dhid = ops.gemm_nt(dout, cache.wt(w_proj), epi=ops.EPI_DACT, act=cfg.act, aux=hpre)
+        dy = ops.gemm_nt(dhid, cache.wt(w_fc))
+        da, d_ln_w, d_ln_b = ops.layernorm_bwd(a, cache.f32(ln_w), dy, dres=dout, eps=cfg.eps)
+        dheads = ops.gemm_nt(da, cache.wt(w_out))                            # [B, D]
+        wt_in = cache.wt(w_in)                                               # [D, 3D]
+        dz = torch.empty((B, H, D), device=x.device, dtype=f32)
+        for h in range(H):                                                   # head_h = Wv_h z[b,h,:] + bv_h
+            ops.gemm_nt(dheads[:, h * dh:(h + 1) * dh], wt_in[:, 2 * D + h * dh:2 * D + (h + 1) * dh], out_f32=True, out=dz[:, h])
+        # every weight gradient that does not wait for dU - BEFORE the token-level launch: their split-M workspaces and the B-row
+        # tensors are gone by the time dx, the head's one [B*L]-row tensor, is allocated
+        d_proj = ops.gemm_tn(out, dfb, f32)
+        d_w_proj, d_b_proj = ops.gemm_tn(dout, g, w_proj.dtype, want_colsum=True)
+        d_w_fc, d_b_fc = ops.gemm_tn(dhid, y, w_fc.dtype, want_colsum=True)
+        d_w_out, d_b_out = ops.gemm_tn(da, heads, w_out.dtype, want_colsum=True)
+        # dWv_h = dheads[:, head h]^T z[:, h, :] per head, on DENSE copies of the two B-row operands: ops.gemm_tn reads whole
+        # 256-column images of its operands, so it is not handed column windows of a wider matrix
+        wv_parts = [ops.gemm_tn(dheads[:, h * dh:(h + 1) * dh].contiguous(), zb[:, h].contiguous(), f32, want_colsum=True)
+                    for h in range(H)]
+        d_wv, d_bv = torch.cat([w for w, _ in wv_parts]), torch.cat([b for _, b in wv_parts])
+        del wv_parts
+        del zb, heads, a, y, hpre, g, out, dfb, dout, dhid, dy, da, dheads
+        dx, du = ops.mappool_bwd(x, u, z, stats, dz, B, L, H)
+        del dz
+        # U = Qs Wk, Qs[h, j] = dh^-0.5 q[j] on head h's channels, q = probe Wq^T + bq
+        dub = ops.to_bf16(du)
+        d_wk = ops.gemm_tn(qs, dub, f32)                                     # dWk[j, d] = Qs[h(j), j] dU[h(j), d]
+        dqs = ops.gemm_nt(dub, cache.w(w_in)[D:2 * D], out_f32=True)         # [H, D(j)] = sum_d dU[h, d] Wk[j, d]
+        dq = (dqs * mask).sum(0, keepdim=True) * float(dh) ** -0.5           # [1, D]: the head's own row of each channel
+        dqb = ops.to_bf16(dq)
+        d_wq = ops.gemm_tn(dqb, ops.to_bf16(probe.detach().reshape(1, D)), f32)
+        d_probe = ops.gemm_nt(dqb, wt_in[:, :D], out_f32=True).reshape(probe.shape)
+        d_w_in = torch.cat([d_wq, d_wk, d_wv])
+        d_b_in = torch.cat([dq[0], torch.zeros_like(dq[0]), d_bv])           # d bk = 0: bk cancels in the softmax
+        grads = (d_probe, d_w_in, d_b_in, d_w_out, d_b_out, d_ln_w, d_ln_b, d_w_fc, d_b_fc, d_w_proj, d_b_proj, d_proj)
+        grads = tuple(_like_param(gr, p) if p.requires_grad else None for gr, p in zip(grads, ctx.params))
+        return (dx, None, None) + grads
 
 
 class L2NormFn(torch.autograd.Function):

@@ -88,6 +88,10 @@ SIGNATURES = {
     "clipa_simce_distill_bwd": (_I32, [_P] * 4 + [_I64] * 8 + [_P, _P, _I64, _F] + [_P] * 5 + [_I64, _P, _P, _I64, _P]),
     "clipa_simsig_workspace": (_I64, [_I64, _I64]),
     "clipa_simsig": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64, _F, _P, _P, _I64, _P, _P, _P, _I64, _P]),
+    # multihead attention pooling, clipa_jax/models/vit.py:187-207 (csrc/mappool.hip)
+    "clipa_mappool_bwd_workspace": (_I64, [_I64, _I64, _I64, _I64]),
+    "clipa_mappool_fwd": (_I32, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P]),
+    "clipa_mappool_bwd": (_I32, [_P] * 7 + [_I64] * 7 + [_P, _I64, _P]),
     "clipa_sum_scale": (_I32, [_P, _P, _I64, _F, _I32, _P]),
     "clipa_retrieval_ranks_workspace": (_I64, [_I64]),
     "clipa_retrieval_ranks": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _I64, _P]),

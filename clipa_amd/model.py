@@ -155,6 +155,42 @@ class _ResBlockParams(nn.Module):
         raise RuntimeError("parameter holder: computed by clipa_amd.engine.ResBlockFn")
 
 
+class _MapHeadParams(nn.Module):
+    """Parameter holder of the multihead attention pooling head (clipa_jax/models/vit.py:187-207, MAPHead): the learned query
+    `probe` [1,1,D], an nn.MultiheadAttention as the holder of the four attention matrices (attn.in_proj_weight / in_proj_bias /
+    out_proj, as in _ResBlockParams), the LayerNorm `ln` and the MLP `mlp.c_fc` / `mlp.c_proj` of width int(D * mlp_ratio).
+    Initialisation: xavier-uniform for the probe, each of the four attention matrices and the two MLP matrices, zero biases, LayerNorm
+    ones / zeros.  The LayerNorm runs with the engine's eps 1e-5 (flax's default, which the JAX model uses, is 1e-6)."""
+
+    def __init__(self, d_model, n_head, mlp_ratio=4.0):
+        super().__init__()
+        self.probe = nn.Parameter(torch.empty(1, 1, d_model))
+        self.attn = nn.MultiheadAttention(d_model, n_head)
+        self.ln = nn.LayerNorm(d_model)
+        mlp_width = int(d_model * mlp_ratio)
+        self.mlp = nn.Sequential(OrderedDict([
+            ("c_fc", nn.Linear(d_model, mlp_width)),
+            ("c_proj", nn.Linear(mlp_width, d_model)),
+        ]))
+        with torch.no_grad():
+            nn.init.xavier_uniform_(self.probe)
+            for i in range(3):
+                nn.init.xavier_uniform_(self.attn.in_proj_weight[i * d_model:(i + 1) * d_model])
+            for lin in (self.attn.out_proj, self.mlp.c_fc, self.mlp.c_proj):
+                nn.init.xavier_uniform_(lin.weight)
+                nn.init.zeros_(lin.bias)
+            nn.init.zeros_(self.attn.in_proj_bias)
+
+    def param_tuple(self):
+        """The head's tensors in the order engine.MapHeadFn reads them."""
+        return (self.probe, self.attn.in_proj_weight, self.attn.in_proj_bias, self.attn.out_proj.weight, self.attn.out_proj.bias,
+                self.ln.weight, self.ln.bias, self.mlp.c_fc.weight, self.mlp.c_fc.bias, self.mlp.c_proj.weight,
+                self.mlp.c_proj.bias)
+
+    def forward(self, *a, **k):
+        raise RuntimeError("parameter holder: computed by clipa_amd.engine.MapHeadFn")
+
+
 # What a block keeps for its backward besides its input (engine.BlockCfg.keep): "light" = the GEMM / attention outputs qkv, a
 # (with the softmax statistics), x1 and the bf16 MLP pre-activation h - the LayerNorm outputs and the activation are
 # re-materialised in backward; "light8" = light with h as saturating e4m3 bytes written by the c_fc epilogue itself (14 instead
@@ -261,7 +297,9 @@ def patch_dropout_indices(batch, num_tokens, prob):
 
 
 class VisionTransformer(nn.Module):
-    """transformer.py:329-534 (patch-embed ViT, cls/GAP pooling, ln_post, proj)."""
+    """transformer.py:329-534 (patch-embed ViT, cls/GAP pooling, ln_post, proj).  pool_style 'big_vision_map': the multihead
+    attention pooling head of the JAX model (clipa_jax/models/vit.py:187-207,282-284) on the tower's un-normalised output -
+    `map_head` instead of `ln_post` (no ln_post parameters or state_dict keys), then `proj`."""
 
     def __init__(self, image_size, patch_size, width, layers, heads, mlp_ratio, output_dim, global_average_pool=False,
                  act=ops.ACT_GELU_ERF, pos_embed='learnable', ln_pre=True, pool_style='open_clip', cache=None,
@@ -291,10 +329,17 @@ class VisionTransformer(nn.Module):
         self.transformer = Transformer(width, layers, heads, mlp_ratio, act=act, ls_init_value=ls_init_value)
         self.global_average_pool = global_average_pool
         self.attn_pool = None
-        self.ln_post = nn.LayerNorm(width)
-        self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
-        if pool_style not in ('open_clip', 'big_vision_tok', 'big_vision_gap'):
+        if pool_style not in ('open_clip', 'big_vision_tok', 'big_vision_gap', 'big_vision_map'):
             raise ValueError(pool_style)
+        if pool_style == 'big_vision_map':
+            if global_average_pool:
+                raise ValueError("pool_style='big_vision_map' pools by attention: global_average_pool must be False")
+            if heads > 16:
+                _unsupported(f"attention pooling with {heads} heads (the fused pooling kernel takes up to 16)")
+            self.map_head = _MapHeadParams(width, heads, mlp_ratio)
+        else:
+            self.ln_post = nn.LayerNorm(width)
+        self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
         self.pool_style = pool_style
         self.image_mean, self.image_std = OPENAI_DATASET_MEAN, OPENAI_DATASET_STD
         self._cache = cache if cache is not None else engine.WeightCache()
@@ -305,7 +350,9 @@ class VisionTransformer(nn.Module):
             p.requires_grad = False
         if unlocked_groups != 0:
             groups = [[self.conv1, self.class_embedding, self.positional_embedding, self.ln_pre],
-                      *self.transformer.resblocks[:-1], [self.transformer.resblocks[-1], self.ln_post], self.proj]
+                      *self.transformer.resblocks[:-1],
+                      [self.transformer.resblocks[-1], self.map_head if self.pool_style == 'big_vision_map' else self.ln_post],
+                      self.proj]
 
             def _unlock(x):
                 if isinstance(x, (list, tuple)):
@@ -355,6 +402,11 @@ class VisionTransformer(nn.Module):
             rows = torch.cat([torch.zeros(B, 1, dtype=torch.int64), keep + 1], dim=1) + torch.arange(B).view(B, 1) * L
             x0 = engine.TokenDropFn.apply(x0, rows.reshape(-1).to(x0.device, non_blocking=True))
             L = 1 + keep.shape[1]
+        if self.pool_style == 'big_vision_map':
+            # every token reaches the head: the whole tower runs, then the folded attention pooling (engine.MapHeadFn)
+            xL = self.transformer.run(x0, B, L, False, self._cache)
+            mcfg = engine.MapHeadCfg(B=B, L=L, H=self.transformer.heads, act=self.transformer.act, eps=1e-5)
+            return engine.MapHeadFn.apply(xL, mcfg, self._cache, *self.map_head.param_tuple(), self.proj)
         if self._pool_mode() == ops.POOL_FIRST:
             # the head reads the class token only: the last block computes that row alone (engine.LastBlockFn)
             rows = torch.arange(B, device=x0.device, dtype=torch.int64) * L

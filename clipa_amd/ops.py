@@ -939,6 +939,50 @@ def pool_bwd(dout, B, L, mode, idx=None):
     return dx
 
 
+def _chk_mappool(who, x, u, B, L, H):
+    _chk(x, bf16, "x", 2)
+    _chk(u, bf16, "u", 2)
+    D = x.shape[1]
+    if not 1 <= H <= 16 or D % 64 or not 64 <= D <= 2048 or L < 1:
+        raise RuntimeError(f"clipa_amd.ops.{who}: unsupported shape H={H}, D={D}, L={L} (1 <= H <= 16, D a multiple of 64 up to "
+                           f"2048, L >= 1)")
+    if x.shape[0] != B * L or tuple(u.shape) != (H, D):
+        raise RuntimeError(f"clipa_amd.ops.{who}: x {tuple(x.shape)} / u {tuple(u.shape)} do not match B={B}, L={L}, H={H}")
+    u = u.contiguous()
+    x, ldx = _aligned16(x)
+    if ldx % 8:      # a row stride the 16-byte loads cannot take: copied, like a misaligned base
+        x, ldx = x.contiguous(), D
+    return x, ldx, u if u.data_ptr() % 16 == 0 else u.clone(), D
+
+
+def mappool_fwd(x, u, B, L, H, _max_workgroups=0):
+    """Folded multihead attention pooling (clipa_jax/models/vit.py:187-207; csrc/mappool.hip): x bf16 [B*L, D] (a row-strided or
+    misaligned view is copied), u bf16 [H, D] -> (z f32 [B,H,D] = sum_l softmax_l(x u_h^T) x, stats f32 [B,H,2] = (max, sum))."""
+    x, ldx, u, D = _chk_mappool("mappool_fwd", x, u, B, L, H)
+    z = torch.empty((B, H, D), device=x.device, dtype=f32)
+    stats = torch.empty((B, H, 2), device=x.device, dtype=f32)
+    with _Timed("mappool_fwd", 4.0 * B * L * H * D, 2.0 * B * L * D + 4.0 * B * H * D, f"{B},{L},{D},{H}"):
+        lib.call("clipa_mappool_fwd", _p(x), _p(u), _p(z), _p(stats), B, L, D, H, ldx, int(_max_workgroups), _stream())
+    return z, stats
+
+
+def mappool_bwd(x, u, z, stats, dz, B, L, H, _max_workgroups=0):
+    """-> (dx bf16 [B*L, D], du f32 [H, D]) of mappool_fwd; du is summed over per-workgroup partials in a fixed order."""
+    x, ldx, u, D = _chk_mappool("mappool_bwd", x, u, B, L, H)
+    for name, t, shape in (("z", z, (B, H, D)), ("stats", stats, (B, H, 2)), ("dz", dz, (B, H, D))):
+        _chk(t, f32, name, 3)
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"clipa_amd.ops.mappool_bwd: {name} {tuple(t.shape)} is not {shape}")
+    z, stats, dz = z.contiguous(), stats.contiguous(), dz.contiguous()
+    dx = torch.empty((B * L, D), device=x.device, dtype=bf16)
+    du = torch.empty((H, D), device=x.device, dtype=f32)
+    ws, wsb = _workspace("clipa_mappool_bwd_workspace", B, H, D, int(_max_workgroups), device=x.device, floor=16)
+    with _Timed("mappool_bwd", 10.0 * B * L * H * D, 4.0 * B * L * D + 8.0 * B * H * D, f"{B},{L},{D},{H}"):
+        lib.call("clipa_mappool_bwd", _p(x), _p(u), _p(z), _p(stats), _p(dz), _p(dx), _p(du), B, L, D, H, ldx, D,
+                 int(_max_workgroups), _p(ws), wsb, _stream())
+    return dx, du
+
+
 def gather_rows(x, rows):
     """out[r] = x[rows[r]]: bf16 [n_src, D], int64 device row list -> bf16 [len(rows), D] (PatchDropout's token selection)."""
     _chk(x, bf16, "x", 2)

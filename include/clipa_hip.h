@@ -340,6 +340,21 @@ int clipa_simsig(const void* rows, const void* cols, int64_t R, int64_t N, int64
                  const float* scale, const float* bias, int64_t label0, float gscale, float* loss_rows,
                  void* dlogits_bf16, int64_t ldd, float* dscale_rows, float* dbias_rows, void* workspace,
                  int64_t workspace_bytes, void* stream);
+/* Multihead attention pooling, the "map" head of clipa_jax/models/vit.py:187-207, token-level part.  The head has one
+ * learned query for every sample, so the K / V projections fold out: with U[H,D] = dh^-0.5 Wk_h^T q_h (bf16),
+ * s[b,l,h] = x[b,l,:] . U[h,:], p = softmax over l, z[b,h,:] = sum_l p[b,l,h] x[b,l,:].  x bf16 [B*L, ldx] (ldx >= D, a
+ * multiple of 8), read once.  fwd -> z f32 [B,H,D], stats f32 [B,H,2] (row max, sum of exp).  bwd (clipa_jax/models/
+ * vit.py:187-207 differentiated through the same fold): from x, U, z, stats and dz f32 [B,H,D] -> dx bf16 [B*L, lddx]
+ * (every row written once) and dU f32 [H,D], summed over per-workgroup partials in a fixed order (no atomics: bit-identical
+ * from run to run at a given B and max_workgroups).  P, dS and dz are rounded to bf16 as MFMA operands.  1 <= H <= 16,
+ * D % 64 == 0, 64 <= D <= 2048, L >= 1; B <= 0 returns OK (bwd: dU = 0).  max_workgroups <= 0: the library's default.
+ * Workspace (bwd): clipa_mappool_bwd_workspace(B, H, D, max_workgroups) bytes.  Pointers 16-byte aligned. */
+int64_t clipa_mappool_bwd_workspace(int64_t B, int64_t H, int64_t D, int64_t max_workgroups);
+int clipa_mappool_fwd(const void* x, const void* U, float* z, float* stats, int64_t B, int64_t L, int64_t D, int64_t H,
+                      int64_t ldx, int64_t max_workgroups, void* stream);
+int clipa_mappool_bwd(const void* x, const void* U, const float* z, const float* stats, const float* dz, void* dx, float* dU,
+                      int64_t B, int64_t L, int64_t D, int64_t H, int64_t ldx, int64_t lddx, int64_t max_workgroups,
+                      void* workspace, int64_t workspace_bytes, void* stream);
 int clipa_sum_scale(const float* in, float* out, int64_t n, float scale, int accumulate, void* stream);
 /* Retrieval ranks of the validation metrics (get_clip_metrics, clipa_torch/training/train.py:432-449) without the [N, N]
  * logit matrix.  A (image features) and B (text features) are fp32 [N, E] with leading dimensions lda, ldb (>= E, multiples
