@@ -79,13 +79,21 @@ def _like_param(g, p):
     return g if g.dtype == p.dtype else g.to(p.dtype)
 
 
+def _finish_grads(grads, params, P=None):
+    """The gradient tuple an autograd.Function returns for `params`: the LayerScale unfold of a block (P: its operands), each
+    gradient in its parameter's dtype, None for a frozen or absent parameter and where nothing was computed."""
+    if P is not None:
+        grads = _unfold_layerscale(P, grads)
+    return tuple(_like_param(g, p) if g is not None and p is not None and p.requires_grad else None for g, p in zip(grads, params))
+
+
 # ---------------------------------------------------------------------------------------------
 @dataclasses.dataclass(frozen=True)
 class BlockCfg:
     """A residual block's settings, built by model.Transformer.run.  keep: what the block stores for its backward besides its
     input - "qkv", "a" (attention output + softmax statistics), "x1", "h" (bf16 MLP pre-activation) or "h8" (the same as saturating
-    e4m3 bytes written by the c_fc epilogue); the bf16 backward-time recompute adds "h1", "h2", "g" (LayerNorm outputs and the
-    activation, _KEEP_ALL).  fp8 blocks: grad_fmt = ops.FMT_* of the gradient operands, predict = the fp8_predicted_scales knob,
+    e4m3 bytes written by the c_fc epilogue); the bf16 backward-time recompute adds the LayerNorm outputs and the activation
+    that its launches leave behind (Inter, _fill).  fp8 blocks: grad_fmt = ops.FMT_* of the gradient operands, predict = the fp8_predicted_scales knob,
     handoff = the tower's GradHandoff; offer: the LayerNorm-1 backward hands dx to the block in front (not a tower's first)."""
     B: int
     L: int
@@ -102,7 +110,33 @@ class BlockCfg:
     offer: bool
 
 
-_KEEP_ALL = frozenset(("h1", "qkv", "a", "x1", "h2", "h", "g"))
+@dataclasses.dataclass
+class Inter:
+    """A block's intermediates, named as in BlockCfg.keep: LayerNorm-1 output, qkv, attention output and softmax statistics, x1 =
+    x + out_proj(a), LayerNorm-2 output, MLP pre-activation (bf16, or e4m3 bytes: "h8") and activation.  None: not there - not
+    kept, not made yet, or already handed on.  The fp8 engine has qkv, a, stats, x1 and hpre only."""
+    h1: object = None
+    qkv: object = None
+    a: object = None
+    stats: object = None
+    x1: object = None
+    h2: object = None
+    hpre: object = None
+    g: object = None
+
+    def kept(self, keep):
+        """What a block stores of these for its backward: the tensors `keep` names; the statistics and the pre-activation are
+        there only where "a" / "h" / "h8" made the forward ask for them."""
+        return Inter(stats=self.stats, hpre=self.hpre,
+                     **{k: getattr(self, k) for k in ("h1", "qkv", "a", "x1", "h2", "g") if k in keep})
+
+    def take(self, *names):
+        """-> the named tensors, which leave the container: the taker's locals are then their only owners, and its `del` frees
+        them where it stands."""
+        vals = [getattr(self, n) for n in names]
+        for n in names:
+            setattr(self, n, None)
+        return vals
 
 
 def _attn_fwd(qkv, cfg, want_stats):
@@ -120,28 +154,58 @@ def _attn_bwd(qkv, a, da, stats, cfg):
     return ops.attention_bwd(qkv, a, da, stats, cfg.B, cfg.L, cfg.H, cfg.causal)
 
 
-def _block_forward(x, P, cfg, keep, need_y=True):
-    """x [M,D] bf16. P: dict of operand tensors. keep: BlockCfg.keep, or _KEEP_ALL.  Returns y and (if keep) the
-    intermediates (h1, qkv, a, stats, x1, h2, hpre, g), None where not kept: the backward re-materialises them."""
-    h1 = ops.layernorm_fwd(x, P["ln1_w"], P["ln1_b"], cfg.eps)
-    qkv = ops.gemm_nt(h1, P["w_in"], P["b_in"])
-    a, stats = _attn_fwd(qkv, cfg, "a" in keep)
-    x1 = ops.gemm_nt(a, P["w_out"], P["b_out"], epi=ops.EPI_ADD, aux=x)
-    h2 = ops.layernorm_fwd(x1, P["ln2_w"], P["ln2_b"], cfg.eps)
-    want_pre = "e4m3" if "h8" in keep else "h" in keep
+# ---- the half-block stages, bf16.  A stage sees operands (P), a few settings and rows: all tokens of a tower or B gathered rows
+def _in_proj(x, P, eps):
+    """LayerNorm-1 + in-projection -> (h1, qkv)."""
+    h1 = ops.layernorm_fwd(x, P["ln1_w"], P["ln1_b"], eps)
+    return h1, ops.gemm_nt(h1, P["w_in"], P["b_in"])
+
+
+def _out_proj(a, x, P):
+    """x1 = x + out_proj(a)."""
+    return ops.gemm_nt(a, P["w_out"], P["b_out"], epi=ops.EPI_ADD, aux=x)
+
+
+def _fc(x1, P, act, eps, want_pre):
+    """LayerNorm-2 + c_fc + activation -> (h2, g, hpre); want_pre: False (hpre = None), True (the bf16 pre-activation) or "e4m3"
+    (the same as saturating e4m3 bytes written by the epilogue)."""
+    h2 = ops.layernorm_fwd(x1, P["ln2_w"], P["ln2_b"], eps)
     if want_pre:
-        g, hpre = ops.gemm_nt(h2, P["w_fc"], P["b_fc"], epi=ops.EPI_ACT, act=cfg.act, want_pre=want_pre)
+        g, hpre = ops.gemm_nt(h2, P["w_fc"], P["b_fc"], epi=ops.EPI_ACT, act=act, want_pre=want_pre)
     else:
-        g, hpre = ops.gemm_nt(h2, P["w_fc"], P["b_fc"], epi=ops.EPI_ACT, act=cfg.act), None
-    # (need_y=False: the backward-time recompute of a block wants the intermediates only - its output is the next block's input,
-    # which that block kept; the c_proj GEMM would be thrown away)
-    y = ops.gemm_nt(g, P["w_proj"], P["b_proj"], epi=ops.EPI_ADD, aux=x1) if need_y else None
-    if not keep:
-        return y, None
-    return y, (h1 if "h1" in keep else None, qkv if "qkv" in keep else None, a if "a" in keep else None, stats,
-               x1 if "x1" in keep else None, h2 if "h2" in keep else None, hpre, g if "g" in keep else None)
+        g, hpre = ops.gemm_nt(h2, P["w_fc"], P["b_fc"], epi=ops.EPI_ACT, act=act), None
+    return h2, g, hpre
 
 
+def _proj(g, x1, P):
+    """y = x1 + c_proj(g)."""
+    return ops.gemm_nt(g, P["w_proj"], P["b_proj"], epi=ops.EPI_ADD, aux=x1)
+
+
+def _fill(x, it, P, cfg, want_stats=True, want_pre=True):
+    """Whatever `it` lacks of qkv, attention output + statistics, x1 and the MLP pre-activation (with the LayerNorm outputs and
+    the activation their launches leave behind), made bit for bit as the forward makes it.  The defaults are the backward's: a
+    "medium" block re-runs LN2 + c_fc (one GEMM instead of four + attention), a block that kept nothing re-runs everything but
+    c_proj - its output is the next block's input, which that block kept.  The forward fills from nothing and asks only for
+    what it keeps (want_stats, want_pre)."""
+    if it.qkv is None:
+        it.h1, it.qkv = _in_proj(x, P, cfg.eps)
+    if it.a is None:
+        it.a, it.stats = _attn_fwd(it.qkv, cfg, want_stats)
+    if it.x1 is None:
+        it.x1 = _out_proj(it.a, x, P)
+    if it.hpre is None:
+        it.h2, it.g, it.hpre = _fc(it.x1, P, cfg.act, cfg.eps, want_pre)
+
+
+def _block_forward(x, P, cfg, keep):
+    """x [M,D] bf16. P: dict of operand tensors. keep: BlockCfg.keep.  -> (y, the intermediates the block keeps, None: no scales)."""
+    it = Inter()
+    _fill(x, it, P, cfg, want_stats="a" in keep, want_pre="e4m3" if "h8" in keep else "h" in keep)
+    return _proj(it.g, it.x1, P), it.kept(keep), None
+
+
+# ---- the fp8 engine ----------------------------------------------------------------------------------------------------------
 def _lin8(xq, xs, P, name, **kw):
     """fp8 linear: row-quantised activation (xq, xs) against the cached row-quantised weight."""
     wq, ws = P["w8_" + name]
@@ -169,68 +233,74 @@ def _wgrad8(dq, ds, sx, emit, out_dtype, cfg):
     return ops.gemm_tn_f8(dq, emit(ds, t), t=t, fmt_p=cfg.grad_fmt, out_dtype=out_dtype)
 
 
-def _block_forward_fp8(x, P, cfg, keep):
-    """_block_forward with the four linear layers on the fp8 MFMA path (BASELINE.json configs[3]): the LayerNorms emit the
-    e4m3 operand of the GEMM that follows them, the attention output and the MLP activation are quantised per token by
-    clipa_quantize_rows; everything between the GEMMs (residual stream, attention, softmax statistics, kept tensors) is
-    bf16 exactly as in the bf16 engine.  keep: the names of BlockCfg.keep; the LayerNorm outputs and the activation are never
-    kept (the fp8 backward re-materialises them as e4m3 operands).  -> (y, kept (qkv, a, stats, x1, hpre) | None, scales):
-    scales = the per-token scales (s1, sa, s2, sg) of the four GEMM inputs (LN1 output, attention output, LN2 output,
-    activation), a few MB that every block keeps - the fp8 weight gradients of the backward derive their tensor scale from
-    them (_wgrad8)."""
-    _, q1, s1 = ops.layernorm_fwd_q8(x, P["ln1_w"], P["ln1_b"], cfg.eps)
-    qkv = _lin8(q1, s1, P, "in")
-    del q1
-    a, stats = _attn_fwd(qkv, cfg, "a" in keep)
+def _in_proj_fp8(x, P, eps):
+    """LayerNorm-1 (emitting the e4m3 operand) + in-projection -> (qkv, s1: the LayerNorm output's per-token scale)."""
+    _, q1, s1 = ops.layernorm_fwd_q8(x, P["ln1_w"], P["ln1_b"], eps)
+    return _lin8(q1, s1, P, "in"), s1
+
+
+def _out_proj_fp8(a, x, P):
+    """x1 = x + out_proj(a) -> (x1, sa: the attention output's per-token scale)."""
     qa, sa = ops.quantize_rows(a)
-    x1 = _lin8(qa, sa, P, "out", epi=ops.EPI_ADD, aux=x)
-    del qa
-    want_pre = "e4m3" if "h8" in keep else "h" in keep
+    return _lin8(qa, sa, P, "out", epi=ops.EPI_ADD, aux=x), sa
+
+
+def _fc_fp8(x1, P, cfg, want_pre):
+    """LayerNorm-2 + c_fc + activation -> (qg, sg: the activation as e4m3 operand of c_proj; s2: the LayerNorm output's per-token
+    scale; hpre).  want_pre: False / True / "e4m3" as in _fc, or "only" - the backward's rebuild, which wants the bf16
+    pre-activation and nothing else (the weight gradient of c_proj re-materialises the activation as an fp8 operand from it,
+    _block_backward_fp8): LN2 + the c_fc GEMM with a plain epilogue -> (None, None, s2, hpre)."""
     # Engine knob `fp8_predicted_scales` (round 6, off by default): the activation leaves the c_fc GEMM as the e4m3 operand of
     # c_proj (no bf16 copy, no row quantiser pass).  A tile of the GEMM cannot know its row's maximum, so the row scale is PREDICTED: |h[m,c]| <= ||LN2(x1)[m,:]|| * max_c ||W_fc[c,:]|| +
     # max |b_fc| (Cauchy-Schwarz; 1.13 covers the e4m3 rounding of both operands) and |gelu(h)| <= |h| - a rigorous bound, a few
     # binades above the row's true maximum, well inside e4m3's range.  Every tier uses the same scales (bit-identical forwards);
     # ragged shapes run GEMM + scaled quantiser with the same arithmetic.  Price (tests/test_fp8_gpu.py,
     # DESIGN 4): per-tensor gradient cosines against the fp32 reference 0.001-0.009 lower than with the rows' true maxima.
-    if cfg.predict:
+    if cfg.predict and want_pre != "only":
         _, q2, s2, rn2 = ops.layernorm_fwd_q8(x1, P["ln2_w"], P["ln2_b"], cfg.eps, want_rownorm=True)    # (4 bytes per row)
         sg, so = ops.row_bound(rn2, P["wn_fc"], P["bmax_fc"], 1.13)
         r = _lin8(q2, s2, P, "fc", epi=ops.EPI_ACT, act=cfg.act, want_pre=want_pre, out_scale=so)
         qg, hpre = r if want_pre else (r, None)
-    else:      # the default: bf16 activation + a row quantiser with the row's TRUE maximum
-        _, q2, s2 = ops.layernorm_fwd_q8(x1, P["ln2_w"], P["ln2_b"], cfg.eps)
-        r = _lin8(q2, s2, P, "fc", epi=ops.EPI_ACT, act=cfg.act, want_pre=want_pre)
-        g, hpre = r if want_pre else (r, None)
-        qg, sg = ops.quantize_rows(g)
-        del g
-    del q2
-    y = _lin8(qg, sg, P, "proj", epi=ops.EPI_ADD, aux=x1)
-    del qg
-    kept = (qkv if "qkv" in keep else None, a if "a" in keep else None, stats, x1 if "x1" in keep else None, hpre)
-    return y, kept if keep else None, (s1, sa, s2, sg)
+        return qg, sg, s2, hpre
+    _, q2, s2 = ops.layernorm_fwd_q8(x1, P["ln2_w"], P["ln2_b"], cfg.eps)
+    if want_pre == "only":
+        return None, None, s2, _lin8(q2, s2, P, "fc")     # bf16(LN2(x1) W^T + b): what the activation epilogue's second output holds
+    # the default: bf16 activation + a row quantiser with the row's TRUE maximum
+    r = _lin8(q2, s2, P, "fc", epi=ops.EPI_ACT, act=cfg.act, want_pre=want_pre)
+    g, hpre = r if want_pre else (r, None)
+    del r
+    qg, sg = ops.quantize_rows(g)
+    return qg, sg, s2, hpre
 
 
-def _fp8_fill(x, kept, P, cfg):
-    """Whatever an fp8 block did not keep of (qkv, attention output + statistics, x1, pre-activation), recomputed bit for bit
-    as the forward produced it.  The activation itself is never rebuilt in bf16: the weight gradient of c_proj re-materialises
-    it as an fp8 operand from the pre-activation (_block_backward_fp8), so a missing pre-activation costs LN2 + the c_fc GEMM
-    with a plain epilogue."""
-    qkv, a, stats, x1, hpre = kept or (None,) * 5
-    if qkv is None:
-        _, q1, s1 = ops.layernorm_fwd_q8(x, P["ln1_w"], P["ln1_b"], cfg.eps)
-        qkv = _lin8(q1, s1, P, "in")
-        del q1
-    if a is None:
-        a, stats = _attn_fwd(qkv, cfg, True)
-    if x1 is None:
-        qa, sa = ops.quantize_rows(a)
-        x1 = _lin8(qa, sa, P, "out", epi=ops.EPI_ADD, aux=x)
-        del qa
-    if hpre is None:
-        _, q2, s2 = ops.layernorm_fwd_q8(x1, P["ln2_w"], P["ln2_b"], cfg.eps)
-        hpre = _lin8(q2, s2, P, "fc")          # bf16(LN2(x1) W^T + b): what the activation epilogue's second output holds
-        del q2
-    return (qkv, a, stats, x1, hpre)
+def _fill_fp8(x, it, P, cfg, want_stats=True, want_pre="only"):
+    """_fill for an fp8 block: whatever `it` lacks of (qkv, attention output + statistics, x1, pre-activation), made bit for bit
+    as the forward makes it.  -> (qg, (s1, sa, s2, sg)): the e4m3 activation and the per-token scales of the four GEMM inputs
+    (LN1 output, attention output, LN2 output, activation), as far as this call made them - the forward, which fills from
+    nothing, gets all of them; the backward has the forward's and drops these."""
+    s1 = sa = s2 = sg = qg = None
+    if it.qkv is None:
+        it.qkv, s1 = _in_proj_fp8(x, P, cfg.eps)
+    if it.a is None:
+        it.a, it.stats = _attn_fwd(it.qkv, cfg, want_stats)
+    if it.x1 is None:
+        it.x1, sa = _out_proj_fp8(it.a, x, P)
+    if it.hpre is None:
+        qg, sg, s2, it.hpre = _fc_fp8(it.x1, P, cfg, want_pre)
+    return qg, (s1, sa, s2, sg)
+
+
+def _block_forward_fp8(x, P, cfg, keep):
+    """_block_forward with the four linear layers on the fp8 MFMA path (BASELINE.json configs[3]): the LayerNorms emit the
+    e4m3 operand of the GEMM that follows them, the attention output and the MLP activation are quantised per token by
+    clipa_quantize_rows; everything between the GEMMs (residual stream, attention, softmax statistics, kept tensors) is
+    bf16 exactly as in the bf16 engine.  keep: the names of BlockCfg.keep; the LayerNorm outputs and the activation are never
+    kept (the fp8 backward re-materialises them as e4m3 operands).  -> (y, the kept intermediates, scales): scales = the
+    per-token scales (s1, sa, s2, sg) of the four GEMM inputs, a few MB that every block keeps - the fp8 weight gradients of
+    the backward derive their tensor scale from them (_wgrad8)."""
+    it = Inter()
+    qg, scales = _fill_fp8(x, it, P, cfg, want_stats="a" in keep, want_pre="e4m3" if "h8" in keep else "h" in keep)
+    return _lin8(qg, scales[3], P, "proj", epi=ops.EPI_ADD, aux=it.x1), it.kept(keep), scales
 
 
 class GradHandoff:
@@ -260,14 +330,23 @@ class GradHandoff:
         self._slot = None
 
 
-def _block_backward_fp8(x, dy, box, P, cfg, scales, offer):
+def _in_proj_backward_fp8(x, grad, s1, P, cfg):
+    """Input and weight gradient of the in-projection on the fp8 path -> (dh1, d_w_in, d_b_in); the LayerNorm-1 backward that
+    takes dh1 is the caller's.  grad: one-element list holding dqkv, popped: this frame is its only owner and frees it early."""
+    dq, ds, d_b_in = _gradq8(grad.pop(), cfg)
+    d_w_in = _wgrad8(dq, ds, s1, lambda r, t: ops.layernorm_fwd_q8s(x, P["ln1_w"], P["ln1_b"], r, t, cfg.eps), P["dt_w_in"], cfg)
+    return _dlin8(dq, ds, P, "in", cfg), d_w_in, d_b_in
+
+
+def _block_backward_fp8(x, dy, it, P, cfg, scales, offer):
     """Backward of a block in fp8 mode: every matrix product - input gradients AND (round 6) weight gradients - on
     v_mfma_f32_16x16x128_f8f6f4.  Each incoming gradient is quantised once per token (its column sums = the bias gradient ride
     the same pass) and feeds both products of its layer; the activation operand of a weight gradient is emitted as e4m3 by the
-    kernel that re-materialises it anyway (LayerNorm, GELU) with the gradient's token scale folded in (_wgrad8).  offer: hand dx
-    and its fp8 form to the block in front of this one (cfg.handoff)."""
+    kernel that re-materialises it anyway (LayerNorm, GELU) with the gradient's token scale folded in (_wgrad8).  it: the block's
+    intermediates, filled (_fill_fp8) and taken out of it here; offer: hand dx and its fp8 form to the block in front of this
+    one (cfg.handoff).  -> (dx, the twelve gradients in param_tuple() order)."""
     act, eps, fmt = cfg.act, cfg.eps, cfg.grad_fmt
-    qkv, a, stats, x1, hpre = box.pop()
+    qkv, a, stats, x1, hpre = it.take("qkv", "a", "stats", "x1", "hpre")
     s1, sa, s2, sg = scales
     dy = dy.contiguous()
     # y = x1 + c_proj(gelu(hpre)); (dq, ds, colsum[, rownorm: the predicted scales only])
@@ -308,50 +387,32 @@ def _block_backward_fp8(x, dy, box, P, cfg, scales, offer):
     d_w_out = _wgrad8(dq, ds, sa, lambda r, t: ops.scale_quantize_rows(a, r, t), P["dt_w_out"], cfg)
     da = _dlin8(dq, ds, P, "out", cfg)
     del dq, ds
-    dqkv = _attn_bwd(qkv, a, da, stats, cfg)
+    grad = [_attn_bwd(qkv, a, da, stats, cfg)]
     del da, a, qkv, stats
-    dq, ds, d_b_in = _gradq8(dqkv, cfg)
-    del dqkv
-    d_w_in = _wgrad8(dq, ds, s1, lambda r, t: ops.layernorm_fwd_q8s(x, P["ln1_w"], P["ln1_b"], r, t, eps), P["dt_w_in"], cfg)
-    dh1 = _dlin8(dq, ds, P, "in", cfg)
-    del dq, ds
+    dh1, d_w_in, d_b_in = _in_proj_backward_fp8(x, grad, s1, P, cfg)
     if offer:      # the block in front of this one runs the same engine: its backward starts from (q, dq, colsum[, rownorm])
         dx, d_ln1_w, d_ln1_b, q8 = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=dx1, eps=eps, q8_fmt=fmt, want_rownorm=cfg.predict)
         cfg.handoff.offer(dx, q8, fmt)
     else:
         dx, d_ln1_w, d_ln1_b = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=dx1, eps=eps)
-    return dx, _unfold_layerscale(P, (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out, d_ln2_w, d_ln2_b, d_w_fc, d_b_fc,
-                                      d_w_proj, d_b_proj))
+    return dx, (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out, d_ln2_w, d_ln2_b, d_w_fc, d_b_fc, d_w_proj, d_b_proj)
 
 
-def _block_backward(x, dy, box, P, cfg):
-    """box: one-element list holding the intermediates tuple (popped so they can be freed early).  bf16 engines (the fp8 engine:
-    _block_backward_fp8)."""
-    act = cfg.act
-    h1, qkv, a, stats, x1, h2, hpre, g = box.pop()
-    dy = dy.contiguous()
-    # tensors the block did not keep are recomputed here, bit for bit as the forward produced them
-    if qkv is None:
-        h1 = ops.layernorm_fwd(x, P["ln1_w"], P["ln1_b"], cfg.eps)
-        qkv = ops.gemm_nt(h1, P["w_in"], P["b_in"])
-    if a is None:
-        a, stats = _attn_fwd(qkv, cfg, True)
-    if x1 is None:
-        x1 = ops.gemm_nt(a, P["w_out"], P["b_out"], epi=ops.EPI_ADD, aux=x)
-    if hpre is None:     # "medium" block: LN2 + c_fc again (one GEMM instead of four + attention)
-        h2 = ops.layernorm_fwd(x1, P["ln2_w"], P["ln2_b"], cfg.eps)
-        g, hpre = ops.gemm_nt(h2, P["w_fc"], P["b_fc"], epi=ops.EPI_ACT, act=act, want_pre=True)
+def _mlp_backward(dy, it, P, act, eps):
+    """Backward of y = x1 + c_proj(act(c_fc(LN2(x1)))) on the rows of dy -> (dx1, (d_ln2_w, d_ln2_b, d_w_fc, d_b_fc, d_w_proj,
+    d_b_proj)).  Takes x1, h2, hpre and g out of `it` and frees each after its last use.  hpre is there; g and h2 may be missing:"""
+    x1, h2, hpre, g = it.take("x1", "h2", "hpre", "g")
     # "light8" block: the GELU-backward epilogue below reads the e4m3 bytes anyway and writes act(hpre) beside its own output
     # (round 6: one more store per chunk instead of an HBM-bound pass over the same bytes; bit for bit what activation_fwd writes)
-    fuse_act = g is None and hpre is not None and hpre.dtype == torch.uint8
-    if g is None and hpre is not None and not fuse_act:      # "light" block: cheap HBM-bound re-materialisation instead of 4 GEMMs + attention
+    fuse_act = g is None and hpre.dtype == torch.uint8
+    if g is None and not fuse_act:      # "light" block: cheap HBM-bound re-materialisation instead of 4 GEMMs + attention
         g = ops.activation_fwd(hpre, act)
-    # LayerNorm outputs that only the weight gradients still need (h2 of a block that kept or re-materialised its MLP
-    # intermediates, h1 of a block that kept qkv) are written by the LayerNorm BACKWARD pass, which has every row and its
+    # A LayerNorm output that only the weight gradient still needs (h2 of a block that kept its MLP pre-activation; likewise h1
+    # of a block that kept qkv, _block_backward) is written by the LayerNorm BACKWARD pass, which has every row and its
     # statistics in registers anyway (ops.layernorm_bwd(beta=...): bit for bit ln_fwd's output) - one more store per row instead of
     # a second ln_fwd launch over the same rows; the weight gradient of c_fc / the in-projection then follows its LayerNorm
     # backward instead of preceding it.
-    emit2, emit1 = h2 is None, h1 is None
+    emit2 = h2 is None
     # y = x1 + c_proj(g).  The weight gradient goes first: g ([M, 4D], the largest transient of the block) is released before
     # the GELU-backward GEMM allocates its output of the same size
     if fuse_act:         # (here g and dh coexist: dy + g + dh = 1.65 GB more than the block's later peak dh + dh2 + dx1 + h2 + dy)
@@ -366,22 +427,36 @@ def _block_backward(x, dy, box, P, cfg):
         del hpre
     dh2 = ops.gemm_nt(dh, P["wt_fc"])       # [M,D]
     if emit2:
-        dx1, d_ln2_w, d_ln2_b, h2 = ops.layernorm_bwd(x1, P["ln2_w"], dh2, dres=dy, eps=cfg.eps, beta=P["ln2_b"])
+        dx1, d_ln2_w, d_ln2_b, h2 = ops.layernorm_bwd(x1, P["ln2_w"], dh2, dres=dy, eps=eps, beta=P["ln2_b"])
         del dh2, x1
         d_w_fc, d_b_fc = ops.gemm_tn(dh, h2, P["dt_w_fc"], want_colsum=True)
         del dh, h2
     else:
         d_w_fc, d_b_fc = ops.gemm_tn(dh, h2, P["dt_w_fc"], want_colsum=True)
         del dh, h2
-        dx1, d_ln2_w, d_ln2_b = ops.layernorm_bwd(x1, P["ln2_w"], dh2, dres=dy, eps=cfg.eps)
+        dx1, d_ln2_w, d_ln2_b = ops.layernorm_bwd(x1, P["ln2_w"], dh2, dres=dy, eps=eps)
         del dh2, x1
-    # x1 = x + out_proj(a)
+    return dx1, (d_ln2_w, d_ln2_b, d_w_fc, d_b_fc, d_w_proj, d_b_proj)
+
+
+def _out_proj_backward(dx1, a, P):
+    """Backward of x1 = x + out_proj(a) -> (da, d_w_out, d_b_out)."""
     da = ops.gemm_nt(dx1, P["wt_out"])
     d_w_out, d_b_out = ops.gemm_tn(dx1, a, P["dt_w_out"], want_colsum=True)
+    return da, d_w_out, d_b_out
+
+
+def _block_backward(x, dy, it, P, cfg):
+    """it: the block's intermediates, filled (_fill); they are taken out of it so that they can be freed early.  bf16 engines
+    (the fp8 engine: _block_backward_fp8).  -> (dx, the twelve gradients in param_tuple() order)."""
+    dy = dy.contiguous()
+    dx1, d_mlp = _mlp_backward(dy, it, P, cfg.act, cfg.eps)
+    qkv, a, stats, h1 = it.take("qkv", "a", "stats", "h1")
+    da, d_w_out, d_b_out = _out_proj_backward(dx1, a, P)
     dqkv = _attn_bwd(qkv, a, da, stats, cfg)
     del da, a, qkv, stats
     dh1 = ops.gemm_nt(dqkv, P["wt_in"])
-    if emit1:
+    if h1 is None:      # a block that kept qkv: the LayerNorm backward emits h1 (see _mlp_backward)
         dx, d_ln1_w, d_ln1_b, h1 = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=dx1, eps=cfg.eps, beta=P["ln1_b"])
         d_w_in, d_b_in = ops.gemm_tn(dqkv, h1, P["dt_w_in"], want_colsum=True)
         del dqkv, h1
@@ -389,8 +464,7 @@ def _block_backward(x, dy, box, P, cfg):
         d_w_in, d_b_in = ops.gemm_tn(dqkv, h1, P["dt_w_in"], want_colsum=True)
         del dqkv, h1
         dx, d_ln1_w, d_ln1_b = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=dx1, eps=cfg.eps)
-    return dx, _unfold_layerscale(P, (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out, d_ln2_w, d_ln2_b, d_w_fc, d_b_fc,
-                                      d_w_proj, d_b_proj))
+    return dx, (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out) + d_mlp
 
 
 def _fold_layerscale(P, cache, cfg, fp8_names, name, w, b, gamma):
@@ -429,17 +503,26 @@ def _unfold_layerscale(P, grads):
     return tuple(grads)
 
 
+def _mlp_operands(cache, ln_w, ln_b, layers, backward=True):
+    """Operands of a LayerNorm + linear layers: the LayerNorm's affine as f32 ("ln2_w", "ln2_b": the one in front of an MLP) and
+    per (name, weight, bias) layer "w_" ([N,K] bf16), "b_" (f32) and - backward - "wt_" (the transposed [K,N] copy of the input
+    gradient) and "dt_w_" (the dtype its weight gradient is asked for)."""
+    P = {"ln2_w": cache.f32(ln_w), "ln2_b": cache.f32(ln_b)}
+    for name, w, b in layers:
+        P["w_" + name], P["b_" + name] = cache.w(w), cache.f32(b)
+        if backward:
+            P["wt_" + name], P["dt_w_" + name] = cache.wt(w), w.dtype
+    return P
+
+
 def _block_operands(params, cache, cfg, fp8_names=("in", "out", "fc", "proj")):
     """params: _ResBlockParams.param_tuple() - twelve tensors, and the two LayerScale gammas behind them when the block has any."""
     ln1_w, ln1_b, w_in, b_in, w_out, b_out, ln2_w, ln2_b, w_fc, b_fc, w_proj, b_proj = params[:12]
     layers = (("in", w_in, b_in), ("out", w_out, b_out), ("fc", w_fc, b_fc), ("proj", w_proj, b_proj))
     # layers whose operands are the LayerScale-folded ones (_fold_layerscale) instead of the parameter's own copies
     folded = {"out": params[12], "proj": params[13]} if len(params) > 12 else {}
-    P = {"ln1_w": cache.f32(ln1_w), "ln1_b": cache.f32(ln1_b), "ln2_w": cache.f32(ln2_w), "ln2_b": cache.f32(ln2_b)}
-    P.update({"w_" + name: cache.w(w) for name, w, _ in layers if name not in folded})
-    P.update({"wt_" + name: cache.wt(w) for name, w, _ in layers if name not in folded})
-    P.update({"b_" + name: cache.f32(b) for name, _, b in layers if name not in folded})
-    P.update({"dt_w_" + name: w.dtype for name, w, _ in layers if name not in folded})
+    P = _mlp_operands(cache, ln2_w, ln2_b, [layer for layer in layers if layer[0] not in folded])
+    P["ln1_w"], P["ln1_b"] = cache.f32(ln1_w), cache.f32(ln1_b)
     if cfg.fp8:   # e4m3 copies, one scale per output channel of the GEMM they feed (rows of W forward, rows of W^T backward); only
         # of the layers that run on the fp8 path (LastBlockFn: the in-projection alone - its B pooled rows take the bf16 GEMMs)
         for name, w, _ in layers:
@@ -468,16 +551,11 @@ class ResBlockFn(torch.autograd.Function):
     def forward(ctx, x, cfg, cache, *params):
         P = _block_operands(params, cache, cfg)
         needs_grad = any(ctx.needs_input_grad)
-        keep = cfg.keep if needs_grad else frozenset()
-        if cfg.fp8:
-            y, inter, scales = _block_forward_fp8(x, P, cfg, keep)
-            ctx.scales = scales if needs_grad else None
-        else:
-            y, inter = _block_forward(x, P, cfg, keep)
+        y, kept, scales = (_block_forward_fp8 if cfg.fp8 else _block_forward)(x, P, cfg, cfg.keep if needs_grad else frozenset())
         ctx.cfg, ctx.cache, ctx.params = cfg, cache, params
         if needs_grad:
             ctx.save_for_backward(x)
-            ctx.inter = inter
+            ctx.inter, ctx.scales = kept, scales
         return y
 
     @staticmethod
@@ -485,18 +563,15 @@ class ResBlockFn(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         cfg, params = ctx.cfg, ctx.params
         P = _block_operands(params, ctx.cache, cfg)
-        box = [ctx.inter]
-        ctx.inter = None
+        it, ctx.inter = ctx.inter, None
         if cfg.fp8:
             scales, ctx.scales = ctx.scales, None
-            box[0] = _fp8_fill(x, box[0], P, cfg)
-            dx, grads = _block_backward_fp8(x, dy, box, P, cfg, scales, offer=cfg.offer and ctx.needs_input_grad[0])
+            _fill_fp8(x, it, P, cfg)
+            dx, grads = _block_backward_fp8(x, dy, it, P, cfg, scales, offer=cfg.offer and ctx.needs_input_grad[0])
         else:
-            if box[0] is None:
-                box[0] = _block_forward(x, P, cfg, _KEEP_ALL, need_y=False)[1]
-            dx, grads = _block_backward(x, dy, box, P, cfg)
-        grads = tuple(_like_param(g, p) if p.requires_grad else None for g, p in zip(grads, params))
-        return (dx, None, None) + grads
+            _fill(x, it, P, cfg)
+            dx, grads = _block_backward(x, dy, it, P, cfg)
+        return (dx, None, None) + _finish_grads(grads, params, P)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -511,7 +586,7 @@ class LastBlockFn(torch.autograd.Function):
     input gradient - runs on the fp8 path like every other block; the B pooled rows (0.5 % of a block's rows) run the bf16 GEMMs.  Forward values of the pooled rows and all gradients are those of the full
     block (zero rows add nothing to a weight gradient).  `rows`: int64 device tensor [B], row index of the pooled token of each
     sample in x.  The token-level part (qkv, attention output, softmax statistics) is kept or recomputed like any other block's;
-    the B-row part is always kept (a few MB)."""
+    the B-row part is always kept (a few MB).  Both parts are the block's own stages, on M rows and on B rows."""
 
     @staticmethod
     def forward(ctx, x, rows, cfg, cache, *params):
@@ -520,79 +595,65 @@ class LastBlockFn(torch.autograd.Function):
         # token-level tensors this block keeps: the block's keep set like any other block's ("qkv", "a" = attention output +
         # softmax statistics); x1 / the pre-activation exist for the B pooled rows only
         keep = cfg.keep if needs_grad else frozenset()
-        s1_box = [None]
-        qkv, a, stats = LastBlockFn._tokens(x, P, cfg, "a" in keep, box=s1_box)
-        ctx.s1 = s1_box[0] if needs_grad else None
-        a_c, x_c = ops.gather_rows(a, rows), ops.gather_rows(x, rows)
-        x1 = ops.gemm_nt(a_c, P["w_out"], P["b_out"], epi=ops.EPI_ADD, aux=x_c)
-        h2 = ops.layernorm_fwd(x1, P["ln2_w"], P["ln2_b"], cfg.eps)
-        g, hpre = ops.gemm_nt(h2, P["w_fc"], P["b_fc"], epi=ops.EPI_ACT, act=cfg.act, want_pre=True)
-        y = ops.gemm_nt(g, P["w_proj"], P["b_proj"], epi=ops.EPI_ADD, aux=x1)
+        tokens = Inter()
+        s1 = LastBlockFn._fill_tokens(x, tokens, P, cfg, "a" in keep)
+        a_c, x_c = ops.gather_rows(tokens.a, rows), ops.gather_rows(x, rows)
+        small = Inter(a=a_c, x1=_out_proj(a_c, x_c, P))
+        small.h2, small.g, small.hpre = _fc(small.x1, P, cfg.act, cfg.eps, True)
+        y = _proj(small.g, small.x1, P)
         ctx.cfg, ctx.cache, ctx.params = cfg, cache, params
         if needs_grad:
             ctx.save_for_backward(x, rows)
-            ctx.tokens = (qkv if "qkv" in keep else None, a if "a" in keep else None, stats)
-            ctx.small = (a_c, x1, h2, hpre, g)
+            ctx.tokens, ctx.small, ctx.s1 = tokens.kept(keep), small, s1
         return y
 
     @staticmethod
-    def _qkv(x, P, cfg, box=None):
-        """-> qkv; fp8 engines leave the LayerNorm output's per-token scale in box[0] (the weight gradient's tensor scale, _wgrad8)."""
-        if cfg.fp8:
-            _, q1, s1 = ops.layernorm_fwd_q8(x, P["ln1_w"], P["ln1_b"], cfg.eps)
-            if box is not None:
-                box[0] = s1
-            return _lin8(q1, s1, P, "in")
-        return ops.gemm_nt(ops.layernorm_fwd(x, P["ln1_w"], P["ln1_b"], cfg.eps), P["w_in"], P["b_in"])
-
-    @staticmethod
-    def _tokens(x, P, cfg, want_stats, qkv=None, box=None):
-        if qkv is None:
-            qkv = LastBlockFn._qkv(x, P, cfg, box)
-        a, stats = _attn_fwd(qkv, cfg, bool(want_stats))
-        return qkv, a, stats
+    def _fill_tokens(x, it, P, cfg, want_stats):
+        """The token-level part of _fill / _fill_fp8: qkv and the attention output where `it` lacks them.  -> fp8 engines, when
+        qkv was made: the LayerNorm output's per-token scale (the weight gradient's tensor scale, _wgrad8)."""
+        s1 = None
+        if it.qkv is None:
+            if cfg.fp8:
+                it.qkv, s1 = _in_proj_fp8(x, P, cfg.eps)
+            else:
+                it.qkv = _in_proj(x, P, cfg.eps)[1]
+        if it.a is None:
+            it.a, it.stats = _attn_fwd(it.qkv, cfg, want_stats)
+        return s1
 
     @staticmethod
     def backward(ctx, dy):
         x, rows = ctx.saved_tensors
         cfg, params = ctx.cfg, ctx.params
         P = _block_operands(params, ctx.cache, cfg, fp8_names=("in",))
-        a_c, x1, h2, hpre, g = ctx.small
-        ctx.small = None
+        small, ctx.small = ctx.small, None
+        a_c, M = small.a, x.shape[0]
         dy = dy.contiguous()
-        M = x.shape[0]
-        dh = ops.gemm_nt(dy, P["wt_proj"], epi=ops.EPI_DACT, act=cfg.act, aux=hpre)
-        d_w_proj, d_b_proj = ops.gemm_tn(dy, g, P["dt_w_proj"], want_colsum=True)
-        dh2 = ops.gemm_nt(dh, P["wt_fc"])
-        d_w_fc, d_b_fc = ops.gemm_tn(dh, h2, P["dt_w_fc"], want_colsum=True)
-        dx1, d_ln2_w, d_ln2_b = ops.layernorm_bwd(x1, P["ln2_w"], dh2, dres=dy, eps=cfg.eps)
-        da_c = ops.gemm_nt(dx1, P["wt_out"])
-        d_w_out, d_b_out = ops.gemm_tn(dx1, a_c, P["dt_w_out"], want_colsum=True)
-        (qkv, a, stats), ctx.tokens = ctx.tokens, None
-        if qkv is None or a is None:      # whatever the block did not keep is recomputed bit for bit
-            qkv, a2, stats2 = LastBlockFn._tokens(x, P, cfg, True, qkv=qkv) if a is None else (LastBlockFn._qkv(x, P, cfg), a, stats)
-            a, stats = a2, stats2
-        dqkv = _attn_bwd(qkv, a, ops.scatter_rows(da_c, rows, M), stats, cfg)
+        dx1, d_mlp = _mlp_backward(dy, small, P, cfg.act, cfg.eps)
+        da_c, d_w_out, d_b_out = _out_proj_backward(dx1, a_c, P)
+        tokens, ctx.tokens = ctx.tokens, None
+        refilled = tokens.qkv is None or tokens.a is None
+        LastBlockFn._fill_tokens(x, tokens, P, cfg, True)      # whatever the block did not keep is recomputed bit for bit
+        qkv, a, stats = tokens.take("qkv", "a", "stats")
+        # A block that recomputed any of them has always held the attention output and the statistics to the end of its backward
+        # (a second pair of names kept them from the `del` below).  The keep planner's budget is measured against that peak, so
+        # this stays as it is here; letting them go with qkv is one line, and a change of the step's memory profile of its own.
+        held = (a, stats) if refilled else None  # noqa: F841
+        grad = [_attn_bwd(qkv, a, ops.scatter_rows(da_c, rows, M), stats, cfg)]
         del qkv, a, stats
         if cfg.fp8:      # token-level products of the block on the fp8 path: input and weight gradient of the in-projection
             s1, ctx.s1 = ctx.s1, None
-            dq, ds, d_b_in = _gradq8(dqkv, cfg)
-            del dqkv
-            d_w_in = _wgrad8(dq, ds, s1, lambda r, t: ops.layernorm_fwd_q8s(x, P["ln1_w"], P["ln1_b"], r, t, cfg.eps),
-                             P["dt_w_in"], cfg)
-            dh1 = _dlin8(dq, ds, P, "in", cfg)
-            del dq, ds
-        else:
+            dh1, d_w_in, d_b_in = _in_proj_backward_fp8(x, grad, s1, P, cfg)
+        else:      # (not _block_backward's: h1 comes from a second ln_fwd between the two products, not from the LayerNorm backward)
+            dqkv = grad.pop()
             dh1 = ops.gemm_nt(dqkv, P["wt_in"])
             h1 = ops.layernorm_fwd(x, P["ln1_w"], P["ln1_b"], cfg.eps)
             d_w_in, d_b_in = ops.gemm_tn(dqkv, h1, P["dt_w_in"], want_colsum=True)
             del dqkv, h1
         # x1 = x[rows] + out_proj(a[rows]): the residual gradient reaches x at the pooled rows only
         dx, d_ln1_w, d_ln1_b = ops.layernorm_bwd(x, P["ln1_w"], dh1, dres=ops.scatter_rows(dx1, rows, M), eps=cfg.eps)
-        grads = _unfold_layerscale(P, (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out, d_ln2_w, d_ln2_b, d_w_fc, d_b_fc,
-                                       d_w_proj, d_b_proj))
-        grads = tuple(_like_param(gr, p) if p.requires_grad else None for gr, p in zip(grads, params))
-        return (dx, None, None, None) + grads
+        grads = (d_ln1_w, d_ln1_b, d_w_in, d_b_in, d_w_out, d_b_out) + d_mlp
+        return (dx, None, None, None) + _finish_grads(grads, params, P)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -661,12 +722,7 @@ class VisionStemFn(torch.autograd.Function):
             k = C * Pp * Pp
             dw = ops.gemm_tn(dpatch, patches, f32)[:, :k]                     # [D, (ph,pw,c)]
             d_conv = dw.reshape(D, Pp, Pp, C).permute(0, 3, 1, 2).contiguous()
-            d_conv = _like_param(d_conv, conv_w)
-        return (None, None, None, d_conv,
-                _like_param(dcls, cls) if cls.requires_grad else None,
-                _like_param(dpos, pos) if pos.requires_grad else None,
-                _like_param(d_ln_w, ln_w) if (cfg.ln_pre and ln_w.requires_grad) else None,
-                _like_param(d_ln_b, ln_b) if (cfg.ln_pre and ln_b.requires_grad) else None)
+        return (None, None, None) + _finish_grads((d_conv, dcls, dpos, d_ln_w, d_ln_b), ctx.params)
 
 
 class TokenDropFn(torch.autograd.Function):
@@ -702,9 +758,7 @@ class TextStemFn(torch.autograd.Function):
         table, pos = ctx.params
         dtable, dpos = ops.embed_tokens_bwd(ids, dx0.contiguous(), table.shape[0], need_table=table.requires_grad,
                                             need_pos=pos.requires_grad)
-        return (None, None,
-                _like_param(dtable, table) if table.requires_grad else None,
-                _like_param(dpos, pos) if pos.requires_grad else None)
+        return (None, None) + _finish_grads((dtable, dpos), ctx.params)
 
 
 HeadCfg = collections.namedtuple("HeadCfg", "B L mode eps")      # HeadFn: B samples of L rows, pooled by ops.POOL_* `mode`
@@ -736,15 +790,12 @@ class HeadFn(torch.autograd.Function):
         if proj is not None:
             dy = ops.gemm_nt(dfb, cache.w(proj))                              # [B,E] @ proj[D,E]^T -> [B,D]
             if proj.requires_grad:
-                d_proj = _like_param(ops.gemm_tn(y, dfb, f32), proj)          # [D,E]
+                d_proj = _like_param(ops.gemm_tn(y, dfb, f32), proj)          # [D,E] (cast here: the f32 product is gone before dx)
         else:
             dy = dfb
         dpooled, d_ln_w, d_ln_b = ops.layernorm_bwd(pooled, cache.f32(ln_w), dy, eps=cfg.eps)
         dx = ops.pool_bwd(dpooled, cfg.B, cfg.L, cfg.mode, idx)
-        return (dx, None, None, None,
-                _like_param(d_ln_w, ln_w) if ln_w.requires_grad else None,
-                _like_param(d_ln_b, ln_b) if ln_b.requires_grad else None,
-                d_proj)
+        return (dx, None, None, None) + _finish_grads((d_ln_w, d_ln_b, d_proj), ctx.params)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -797,34 +848,39 @@ class MapHeadFn(torch.autograd.Function):
         for h in range(H):
             hs = slice(h * dh, (h + 1) * dh)
             ops.gemm_nt(zb[:, h], wv[hs], bv[hs], out=heads[:, hs])
-        a = ops.gemm_nt(heads, cache.w(w_out), cache.f32(b_out))
-        y = ops.layernorm_fwd(a, cache.f32(ln_w), cache.f32(ln_b), cfg.eps)
-        g, hpre = ops.gemm_nt(y, cache.w(w_fc), cache.f32(b_fc), epi=ops.EPI_ACT, act=cfg.act, want_pre=True)
-        out = ops.gemm_nt(g, cache.w(w_proj), cache.f32(b_proj), epi=ops.EPI_ADD, aux=a)
+        ctx.params = (probe, w_in, b_in, w_out, b_out, ln_w, ln_b, w_fc, b_fc, w_proj, b_proj, proj)
+        P = MapHeadFn._operands(cache, ctx.params, backward=False)      # (a frozen head never builds the transposed copies)
+        mlp = Inter(x1=ops.gemm_nt(heads, P["w_out"], P["b_out"]))            # the out-projection, without a residual
+        mlp.h2, mlp.g, mlp.hpre = _fc(mlp.x1, P, cfg.act, cfg.eps, True)
+        out = _proj(mlp.g, mlp.x1, P)
         feat = ops.gemm_nt(out, cache.wt(proj), out_f32=True)
         ctx.cfg, ctx.cache = cfg, cache
-        ctx.params = (probe, w_in, b_in, w_out, b_out, ln_w, ln_b, w_fc, b_fc, w_proj, b_proj, proj)
         ctx.save_for_backward(x, z, stats)
-        ctx.rows = (zb, heads, a, y, hpre, g, out)      # the B-row tensors: released in backward before dx is allocated
+        ctx.rows = (zb, heads, mlp, out)      # the B-row tensors: released in backward before dx is allocated
         return feat
+
+    @staticmethod
+    def _operands(cache, params, backward=True):
+        """The operands of the head's B-row layers under the names the block's stages read (_mlp_operands)."""
+        _, _, _, w_out, b_out, ln_w, ln_b, w_fc, b_fc, w_proj, b_proj, _ = params
+        return _mlp_operands(cache, ln_w, ln_b, (("out", w_out, b_out), ("fc", w_fc, b_fc), ("proj", w_proj, b_proj)), backward)
 
     @staticmethod
     def backward(ctx, dfeat):
         x, z, stats = ctx.saved_tensors
-        (zb, heads, a, y, hpre, g, out), ctx.rows = ctx.rows, None
+        (zb, heads, mlp, out), ctx.rows = ctx.rows, None
         cfg, cache = ctx.cfg, ctx.cache
-        probe, w_in, b_in, w_out, b_out, ln_w, ln_b, w_fc, b_fc, w_proj, b_proj, proj = ctx.params
+        probe, w_in, b_in, *_, proj = ctx.params
+        P = MapHeadFn._operands(cache, ctx.params)
         B, L, H = cfg.B, cfg.L, cfg.H
         D = x.shape[1]
         dh = D // H
         u, qs, mask = _map_fold(cache, probe, w_in, b_in, H)
-        # the input-gradient chain on B rows down to dz
+        # the input-gradient chain on B rows down to dz, with the weight gradients of the MLP and the out-projection on its way
         dfb = ops.to_bf16(dfeat.contiguous())
         dout = ops.gemm_nt(dfb, cache.w(proj))                               # [B,E] @ proj[D,E]^T -> [B,D]
-        dhid = ops.gemm_nt(dout, cache.wt(w_proj), epi=ops.EPI_DACT, act=cfg.act, aux=hpre)
-        dy = ops.gemm_nt(dhid, cache.wt(w_fc))
-        da, d_ln_w, d_ln_b = ops.layernorm_bwd(a, cache.f32(ln_w), dy, dres=dout, eps=cfg.eps)
-        dheads = ops.gemm_nt(da, cache.wt(w_out))                            # [B, D]
+        da, d_mlp = _mlp_backward(dout, mlp, P, cfg.act, cfg.eps)
+        dheads, d_w_out, d_b_out = _out_proj_backward(da, heads, P)          # [B, D]
         wt_in = cache.wt(w_in)                                               # [D, 3D]
         dz = torch.empty((B, H, D), device=x.device, dtype=f32)
         for h in range(H):                                                   # head_h = Wv_h z[b,h,:] + bv_h
@@ -832,16 +888,13 @@ class MapHeadFn(torch.autograd.Function):
         # every weight gradient that does not wait for dU - BEFORE the token-level launch: their split-M workspaces and the B-row
         # tensors are gone by the time dx, the head's one [B*L]-row tensor, is allocated
         d_proj = ops.gemm_tn(out, dfb, f32)
-        d_w_proj, d_b_proj = ops.gemm_tn(dout, g, w_proj.dtype, want_colsum=True)
-        d_w_fc, d_b_fc = ops.gemm_tn(dhid, y, w_fc.dtype, want_colsum=True)
-        d_w_out, d_b_out = ops.gemm_tn(da, heads, w_out.dtype, want_colsum=True)
         # dWv_h = dheads[:, head h]^T z[:, h, :] per head, on DENSE copies of the two B-row operands: ops.gemm_tn reads whole
         # 256-column images of its operands, so it is not handed column windows of a wider matrix
         wv_parts = [ops.gemm_tn(dheads[:, h * dh:(h + 1) * dh].contiguous(), zb[:, h].contiguous(), f32, want_colsum=True)
                     for h in range(H)]
         d_wv, d_bv = torch.cat([w for w, _ in wv_parts]), torch.cat([b for _, b in wv_parts])
         del wv_parts
-        del zb, heads, a, y, hpre, g, out, dfb, dout, dhid, dy, da, dheads
+        del zb, heads, out, dfb, dout, da, dheads
         dx, du = ops.mappool_bwd(x, u, z, stats, dz, B, L, H)
         del dz
         # U = Qs Wk, Qs[h, j] = dh^-0.5 q[j] on head h's channels, q = probe Wq^T + bq
@@ -854,9 +907,8 @@ class MapHeadFn(torch.autograd.Function):
         d_probe = ops.gemm_nt(dqb, wt_in[:, :D], out_f32=True).reshape(probe.shape)
         d_w_in = torch.cat([d_wq, d_wk, d_wv])
         d_b_in = torch.cat([dq[0], torch.zeros_like(dq[0]), d_bv])           # d bk = 0: bk cancels in the softmax
-        grads = (d_probe, d_w_in, d_b_in, d_w_out, d_b_out, d_ln_w, d_ln_b, d_w_fc, d_b_fc, d_w_proj, d_b_proj, d_proj)
-        grads = tuple(_like_param(gr, p) if p.requires_grad else None for gr, p in zip(grads, ctx.params))
-        return (dx, None, None) + grads
+        grads = (d_probe, d_w_in, d_b_in, d_w_out, d_b_out) + d_mlp + (d_proj,)
+        return (dx, None, None) + _finish_grads(grads, ctx.params)
 
 
 class L2NormFn(torch.autograd.Function):
