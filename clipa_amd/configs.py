@@ -41,6 +41,9 @@ def _builtin():
     # the B/16 tower with the JAX model's multihead attention pooling head (clipa_jax/models/vit.py:187-207), as SigLIP trains it
     cfgs["ViT-B-16-MAP-BigVision"] = _vit("B", 16)
     cfgs["ViT-B-16-MAP-BigVision"]["vision_cfg"].update(pool_style="big_vision_map", gelu_approximate="tanh")
+    # the B/16 tower with dual PatchNorm (input_patchnorm, transformer.py:362-371): LayerNorm over each patch + Linear stem
+    cfgs["ViT-B-16-patchnorm"] = _vit("B", 16)
+    cfgs["ViT-B-16-patchnorm"]["vision_cfg"]["input_patchnorm"] = True
     for ctx in (8, 16):
         cfgs[f"ViT-L-16-CL{ctx}-Syntax-GAP"] = _vit("L", 16, ctx=ctx, gap=True, text_mask="syntax")
     cfgs["ViT-L-16-CL32-GAP"] = _vit("L", 16, ctx=32, gap=True)

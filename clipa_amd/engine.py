@@ -6,6 +6,7 @@ it stands in for (paths relative to /root/reference/clipa_torch):
                  (LayerScale, transformer.py:43-50, folded into out_proj / c_proj: _fold_layerscale)
   LastBlockFn    the same for a tower's last block when the head reads one row per sample (returns those rows only)
   VisionStemFn   conv1 + cls/pos + ln_pre                  open_clip/transformer.py:480-503
+                 (dual PatchNorm, transformer.py:362-371,483-489, folded into the stem GEMM's operands: _fold_patchnorm)
   TokenDropFn    PatchDropout (row selection)              open_clip/transformer.py:53-83,501-502
   TextStemFn     token_embedding + positional_embedding    open_clip/model.py:245-247
   HeadFn         pool + ln_post/ln_final + projection      transformer.py:509-529, model.py:251-260
@@ -668,36 +669,55 @@ def _conv_weight_operand(w, Kp):
 
 
 # VisionStemFn: B images of L tokens, P x P patches (K = 3 P P zero-padded to Kp), mean / std of uint8 images (None: float
-# input), whether ln_pre exists
-StemCfg = collections.namedtuple("StemCfg", "B L P Kp eps ln_pre mean std")
+# input), whether ln_pre exists, patchnorm: dual PatchNorm (input_patchnorm) - a LayerNorm over each patch in front of a Linear
+StemCfg = collections.namedtuple("StemCfg", "B L P Kp eps ln_pre mean std patchnorm", defaults=(False,))
 
 
 def _vision_stem_forward(image, P, cfg):
-    patches = ops.patchify(image, cfg.P, cfg.Kp, cfg.mean, cfg.std)
-    pe = ops.gemm_nt(patches, P["w_conv"])
+    if cfg.patchnorm:      # xhat W'^T + b' == LayerNorm_K(patches) W^T + b (_fold_patchnorm)
+        patches = ops.patchify_ln(image, cfg.P, cfg.Kp, cfg.mean, cfg.std, cfg.eps)
+        pe = ops.gemm_nt(patches, P["w_conv"], P["b_conv"])
+    else:
+        patches = ops.patchify(image, cfg.P, cfg.Kp, cfg.mean, cfg.std)
+        pe = ops.gemm_nt(patches, P["w_conv"])
     tok = ops.assemble_tokens(pe, P["cls"], P["pos"], cfg.B, cfg.L)
     x0 = ops.layernorm_fwd(tok, P["ln_w"], P["ln_b"], cfg.eps) if cfg.ln_pre else tok
     return patches, tok, x0
 
 
+def _fold_patchnorm(cache, cfg, conv_w, conv_b, pn_w, pn_b):
+    """Dual PatchNorm (transformer.py:362-371,483-489: patchnorm_pre_ln = LayerNorm(K), conv1 = nn.Linear(K, width)) folded into
+    the stem GEMM's operands: LayerNorm_K(x) W^T + b == xhat (W diag(gamma))^T + (b + W beta), xhat = (x - mean) * rstd from
+    ops.patchify_ln.  -> (W' bf16 [D,Kp] in the engine's (ph,pw,c) column order, b' f32 [D]); cached under the four parameters
+    together: a step of any of them rebuilds the pair."""
+    return cache.multi((conv_w, conv_b, pn_w, pn_b), "pn%d" % cfg.Kp,
+                       lambda w, b, g, bt: ops.patchnorm_fold(w, cache.f32(conv_b), cache.f32(pn_w), cache.f32(pn_b), cfg.P, cfg.Kp))
+
+
 class VisionStemFn(torch.autograd.Function):
     """uint8/float image -> normalise -> patch GEMM -> [cls; patches] + pos -> ln_pre
-    (train.py:191-197 + transformer.py:480-503)."""
+    (train.py:191-197 + transformer.py:480-503).  cfg.patchnorm: `pn` = (conv1.bias, patchnorm_pre_ln.weight,
+    patchnorm_pre_ln.bias) and conv_w is the Linear's [D, K] matrix; else `pn` is empty and conv_w the convolution's [D,3,P,P]."""
 
     @staticmethod
-    def forward(ctx, image, cfg, cache, conv_w, cls, pos, ln_w, ln_b):
-        P = VisionStemFn._operands(cfg, cache, conv_w, cls, pos, ln_w, ln_b)
+    def forward(ctx, image, cfg, cache, conv_w, cls, pos, ln_w, ln_b, *pn):
+        if len(pn) != (3 if cfg.patchnorm else 0):
+            raise RuntimeError("VisionStemFn: patchnorm takes conv1.bias, patchnorm_pre_ln.weight and patchnorm_pre_ln.bias")
+        P = VisionStemFn._operands(cfg, cache, conv_w, cls, pos, ln_w, ln_b, *pn)
         _, _, x0 = _vision_stem_forward(image, P, cfg)
         ctx.cfg, ctx.cache = cfg, cache
-        ctx.params = (conv_w, cls, pos, ln_w, ln_b)
+        ctx.params = (conv_w, cls, pos, ln_w, ln_b) + pn
         ctx.save_for_backward(image)
         return x0
 
     @staticmethod
-    def _operands(cfg, cache, conv_w, cls, pos, ln_w, ln_b):
+    def _operands(cfg, cache, conv_w, cls, pos, ln_w, ln_b, *pn):
         Kp = cfg.Kp
-        P = {"w_conv": cache.custom(conv_w, "conv%d" % Kp, lambda t: _conv_weight_operand(t, Kp)),
-             "cls": cache.f32(cls), "pos": cache.f32(pos)}
+        if cfg.patchnorm:
+            P = dict(zip(("w_conv", "b_conv"), _fold_patchnorm(cache, cfg, conv_w, *pn)))
+        else:
+            P = {"w_conv": cache.custom(conv_w, "conv%d" % Kp, lambda t: _conv_weight_operand(t, Kp))}
+        P["cls"], P["pos"] = cache.f32(cls), cache.f32(pos)
         if cfg.ln_pre:
             P["ln_w"], P["ln_b"] = cache.f32(ln_w), cache.f32(ln_b)
         return P
@@ -706,8 +726,8 @@ class VisionStemFn(torch.autograd.Function):
     def backward(ctx, dx0):
         (image,) = ctx.saved_tensors
         cfg = ctx.cfg
-        conv_w, cls, pos, ln_w, ln_b = ctx.params
-        P = VisionStemFn._operands(cfg, ctx.cache, conv_w, cls, pos, ln_w, ln_b)
+        conv_w, cls, pos, ln_w, ln_b = ctx.params[:5]
+        P = VisionStemFn._operands(cfg, ctx.cache, *ctx.params)
         patches, tok, _ = _vision_stem_forward(image, P, cfg)
         dx0 = dx0.contiguous()
         d_ln_w = d_ln_b = None
@@ -716,13 +736,28 @@ class VisionStemFn(torch.autograd.Function):
         else:
             dtok = dx0
         dpatch, dcls, dpos = ops.assemble_tokens_bwd(dtok, cfg.B, cfg.L, need_pos=pos.requires_grad)
-        d_conv = None
-        if conv_w.requires_grad:
+        d_conv, d_pn = None, ()
+        if cfg.patchnorm:
+            # G = dPE^T xhat (f32, as the LayerScale layers ask for theirs) and s = colsum(dPE) = d conv1.bias: one reduction
+            # kernel turns them into dW = gamma G + beta s, dgamma = sum_n W G, dbeta = sum_n W s.  No input-gradient GEMM:
+            # the image gets no gradient
+            conv_b, pn_w, pn_b = ctx.params[5:]
+            d_pn = (None, None, None)
+            if any(p.requires_grad for p in (conv_w, conv_b, pn_w, pn_b)):
+                G, s = ops.gemm_tn(dpatch, patches, f32, want_colsum=True)      # [D, Kp (ph,pw,c)], [D]
+                want = (conv_w.requires_grad, pn_w.requires_grad, pn_b.requires_grad)
+                if any(want):
+                    d_conv, d_g, d_b = ops.patchnorm_unfold(G, s, conv_w.detach(), ctx.cache.f32(pn_w), ctx.cache.f32(pn_b), cfg.P,
+                                                            out_dtype=conv_w.dtype, want=want)
+                    d_pn = (s, d_g, d_b)
+                else:
+                    d_pn = (s, None, None)
+        elif conv_w.requires_grad:
             D, C, Pp, _ = conv_w.shape
             k = C * Pp * Pp
             dw = ops.gemm_tn(dpatch, patches, f32)[:, :k]                     # [D, (ph,pw,c)]
             d_conv = dw.reshape(D, Pp, Pp, C).permute(0, 3, 1, 2).contiguous()
-        return (None, None, None) + _finish_grads((d_conv, dcls, dpos, d_ln_w, d_ln_b), ctx.params)
+        return (None, None, None) + _finish_grads((d_conv, dcls, dpos, d_ln_w, d_ln_b) + d_pn, ctx.params)
 
 
 class TokenDropFn(torch.autograd.Function):

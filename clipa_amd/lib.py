@@ -61,6 +61,10 @@ SIGNATURES = {
     "clipa_transpose_to_bf16": (_I32, [_P, _I32, _P, _I64, _I64, _I64, _I64, _P]),
     "clipa_layerscale_fold": (_I32, [_P, _I32, _P, _P, _P, _P, _I64, _I64, _P]),
     "clipa_layerscale_unfold": (_I32, [_P, _P, _I32, _P, _P, _P, _P, _I32, _P, _P, _I64, _I64, _P]),
+    # dual PatchNorm stem, open_clip/transformer.py:362-371,483-489 (csrc/patchnorm.hip)
+    "clipa_patchify_ln": (_I32, [_P, _P, _I64, _I64, _I64, _I64, _I32, _I32, _I32, _c.POINTER(_F), _c.POINTER(_F), _F, _P]),
+    "clipa_patchnorm_fold": (_I32, [_P, _I32, _P, _P, _P, _P, _P, _I64, _I64, _I64, _P]),
+    "clipa_patchnorm_unfold": (_I32, [_P, _P, _P, _I32, _P, _P, _P, _I32, _P, _P, _I64, _I64, _I64, _P]),
     "clipa_activation_fwd": (_I32, [_P, _P, _I64, _I32, _P]),
     "clipa_cast_bf16_to_e4m3": (_I32, [_P, _P, _I64, _P]),
     "clipa_cast_e4m3_to_bf16": (_I32, [_P, _P, _I64, _P]),

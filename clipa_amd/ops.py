@@ -664,13 +664,14 @@ def attention_bwd_varlen(qkv, out, dout, stats, vl, H, causal):
     return dqkv
 
 
-def patchify(img, P, Kp, mean=None, std=None):
-    """img [B,3,S,S] (NCHW or channels_last memory), u8 / bf16 / f32 -> bf16 [B*(S//P)^2, Kp]."""
+def _patch_source(img, mean, std, who):
+    """The image operand of patchify / patchify_ln: -> (tensor in NCHW or channels_last memory, B, S, dtype code, nhwc,
+    normalize, mean[3], std[3] as C arrays)."""
     if not img.is_cuda:
-        raise RuntimeError("patchify: image must be on the GPU")
+        raise RuntimeError(f"{who}: image must be on the GPU")
     B, C, S, S2 = img.shape
     if C != 3 or S != S2:
-        raise RuntimeError(f"patchify: expected [B,3,S,S], got {tuple(img.shape)}")
+        raise RuntimeError(f"{who}: expected [B,3,S,S], got {tuple(img.shape)}")
     if img.is_contiguous():
         nhwc = 0
     elif img.is_contiguous(memory_format=torch.channels_last):
@@ -679,15 +680,101 @@ def patchify(img, P, Kp, mean=None, std=None):
         img, nhwc = img.contiguous(), 0
     dt = {torch.uint8: DT_U8, bf16: DT_BF16, f32: DT_F32}.get(img.dtype)
     if dt is None:
-        raise RuntimeError(f"patchify: unsupported image dtype {img.dtype}")
-    g = S // P
-    out = torch.empty((B * g * g, Kp), device=img.device, dtype=bf16)
+        raise RuntimeError(f"{who}: unsupported image dtype {img.dtype}")
     normalize = mean is not None
     m3 = (ctypes.c_float * 3)(*([float(v) for v in mean] if normalize else [0, 0, 0]))
     s3 = (ctypes.c_float * 3)(*([float(v) for v in std] if normalize else [1, 1, 1]))
+    return img, B, S, dt, nhwc, int(normalize), m3, s3
+
+
+def patchify(img, P, Kp, mean=None, std=None):
+    """img [B,3,S,S] (NCHW or channels_last memory), u8 / bf16 / f32 -> bf16 [B*(S//P)^2, Kp]."""
+    img, B, S, dt, nhwc, normalize, m3, s3 = _patch_source(img, mean, std, "patchify")
+    g = S // P
+    out = torch.empty((B * g * g, Kp), device=img.device, dtype=bf16)
     with _Timed("patchify", 0.0, float(img.numel()) * img.element_size() + 2.0 * out.numel(), f"{B},{S},{P}"):
-        lib.call("clipa_patchify", _p(img), _p(out), B, S, P, Kp, dt, nhwc, int(normalize), m3, s3, _stream())
+        lib.call("clipa_patchify", _p(img), _p(out), B, S, P, Kp, dt, nhwc, normalize, m3, s3, _stream())
     return out
+
+
+def _chk_patch_geometry(P, Kp, who):
+    if P <= 0 or Kp % 8 != 0 or Kp < 3 * P * P or Kp > 3072:
+        raise RuntimeError(f"clipa_amd.ops.{who}: bad geometry P={P} Kp={Kp} (Kp % 8 == 0, 3*P*P <= Kp <= 3072)")
+
+
+def patchify_ln(img, P, Kp, mean=None, std=None, eps=1e-5):
+    """patchify followed by the LayerNorm of dual PatchNorm WITHOUT its affine (transformer.py:483-488): img as for patchify ->
+    bf16 [B*(S//P)^2, Kp] = (x - mean) * rstd per patch row over its 3*P*P elements (fp32 statistics), (ph,pw,c) order, pad
+    columns zero.  A constant patch gives exact zeros."""
+    _chk_patch_geometry(P, Kp, "patchify_ln")
+    img, B, S, dt, nhwc, normalize, m3, s3 = _patch_source(img, mean, std, "patchify_ln")
+    g = S // P
+    if g <= 0:
+        raise RuntimeError(f"clipa_amd.ops.patchify_ln: image size {S} below the patch size {P}")
+    out = torch.empty((B * g * g, Kp), device=img.device, dtype=bf16)
+    with _Timed("patchify_ln", 0.0, float(img.numel()) * img.element_size() + 2.0 * out.numel(), f"{B},{S},{P}"):
+        lib.call("clipa_patchify_ln", _p(img), _p(out), B, S, P, Kp, dt, nhwc, normalize, m3, s3, float(eps), _stream())
+    return out
+
+
+def _chk_patchnorm(w, gamma, beta, P, who):
+    if w.dtype not in (f32, bf16):
+        raise RuntimeError(f"clipa_amd.ops.{who}: w must be torch.float32 or torch.bfloat16, got {w.dtype}")
+    _chk(w, None, "w", 2)
+    K = 3 * P * P
+    if w.shape[1] != K:
+        raise RuntimeError(f"clipa_amd.ops.{who}: w has {w.shape[1]} columns for 3*P*P = {K}")
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        _chk(t, f32, name, 1)
+        if t.shape[0] != K:
+            raise RuntimeError(f"clipa_amd.ops.{who}: {name} has {t.shape[0]} entries for 3*P*P = {K}")
+
+
+def patchnorm_fold(w, b, gamma, beta, P, Kp):
+    """Dual PatchNorm's LayerNorm affine folded into the Linear behind it (transformer.py:368-369,487-488): w [N,K] f32/bf16 and
+    b f32 [N] of conv1, gamma / beta f32 [K] of patchnorm_pre_ln, K = 3*P*P in (c,p1,p2) order -> (bf16 [N,Kp] = bf16(w * gamma)
+    with the columns in (ph,pw,c) order and zero padding, f32 [N] = b + w @ beta); fp32, one rounding, fixed order."""
+    _chk_patch_geometry(P, Kp, "patchnorm_fold")
+    _chk_patchnorm(w, gamma, beta, P, "patchnorm_fold")
+    _chk(b, f32, "b", 1)
+    N = w.shape[0]
+    if b.shape[0] != N:
+        raise RuntimeError(f"clipa_amd.ops.patchnorm_fold: b has {b.shape[0]} entries for {N} rows of w")
+    w, b, gamma, beta = w.contiguous(), b.contiguous(), gamma.contiguous(), beta.contiguous()
+    wf = torch.empty((N, Kp), device=w.device, dtype=bf16)
+    bfold = torch.empty(N, device=w.device, dtype=f32)
+    with _Timed("patchnorm_fold", 2.0 * N * w.shape[1], float(N) * (w.shape[1] * w.element_size() + 2 * Kp)):
+        lib.call("clipa_patchnorm_fold", _p(w), int(w.dtype == f32), _p(b), _p(gamma), _p(beta), _p(wf), _p(bfold), N, P, Kp,
+                 _stream())
+    return wf, bfold
+
+
+def patchnorm_unfold(g, s, w, gamma, beta, P, out_dtype=f32, want=(True, True, True)):
+    """The parameters' gradients of a stem that ran with folded PatchNorm: g f32 [N,Kp] = dPE^T xhat ((ph,pw,c) columns) and
+    s f32 [N] = colsum(dPE) -> (dw [N,K] in out_dtype = gamma * g + beta * s[:,None], dgamma f32 [K] = sum_n w * g, dbeta f32 [K]
+    = sum_n w * s[:,None]), all in the parameters' (c,p1,p2) order; fp32, fixed order over n.  want: which of the three to
+    compute (None in place of the others).  The gradient of conv1.bias is s."""
+    _chk_out_dtype(out_dtype, "patchnorm_unfold")
+    _chk_patchnorm(w, gamma, beta, P, "patchnorm_unfold")
+    _chk(g, f32, "g", 2)
+    N, K = w.shape
+    Kp = g.shape[1]
+    _chk_patch_geometry(P, Kp, "patchnorm_unfold")
+    if g.shape[0] != N:
+        raise RuntimeError(f"clipa_amd.ops.patchnorm_unfold: g {tuple(g.shape)} vs w {tuple(w.shape)}")
+    _chk(s, f32, "s", 1)
+    if s.shape[0] != N:
+        raise RuntimeError(f"clipa_amd.ops.patchnorm_unfold: s has {s.shape[0]} entries for {N} rows of w")
+    want_w, want_g, want_b = (bool(v) for v in want)
+    g, s, w, gamma, beta = g.contiguous(), s.contiguous(), w.contiguous(), gamma.contiguous(), beta.contiguous()
+    dw = torch.empty((N, K), device=w.device, dtype=out_dtype) if want_w else None
+    dg = torch.empty(K, device=w.device, dtype=f32) if want_g else None
+    db = torch.empty(K, device=w.device, dtype=f32) if want_b else None
+    with _Timed("patchnorm_unfold", 4.0 * N * K if want_g or want_b else 0.0,
+                float(N) * K * (4 + (w.element_size() if want_g or want_b else 0) + (dw.element_size() if want_w else 0))):
+        lib.call("clipa_patchnorm_unfold", _p(g), _p(s), _p(w), int(w.dtype == f32), _p(gamma), _p(beta), _p(dw),
+                 int(out_dtype == f32), _p(dg), _p(db), N, P, Kp, _stream())
+    return dw, dg, db
 
 
 def resized_crop_u8(src, boxes, size, gray_flags=None):

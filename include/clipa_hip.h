@@ -296,6 +296,26 @@ int clipa_layerscale_fold(const void* w, int w_f32, const float* gamma, const fl
 int clipa_layerscale_unfold(const float* dw_folded, const void* w, int w_f32, const float* gamma, const float* db_folded,
                             const float* b, void* dw, int dw_f32, float* db, float* dgamma, int64_t N, int64_t K,
                             void* stream);
+/* Dual PatchNorm stem (input_patchnorm, arXiv 2302.01327; open_clip/transformer.py:362-371,483-489: rearrange to
+ * [B, g*g, 3*P*P], patchnorm_pre_ln = LayerNorm(3*P*P, eps 1e-5), conv1 = nn.Linear(3*P*P, width)).  K = 3*P*P.
+ * patchify_ln: clipa_patchify's inputs and geometry (Kp % 8 == 0, 3*P*P <= Kp <= 3072, pixels beyond g*P never read) ->
+ *         bf16 [B*g*g, Kp] = (x - mean) * rstd of every patch row, WITHOUT the affine; columns in (ph,pw,c) order, columns
+ *         >= K zero.  fp32 statistics over the K real elements (mean first, then the centred sum of squares), taken on the row
+ *         minus its first element: a constant patch gives exact zeros.  One wave per patch row, the row in registers.
+ * fold:   gamma / beta f32 [K] of the LayerNorm and w [N,K] (bf16, or f32 if w_f32) / b f32 [N] of the Linear, all in the
+ *         parameters' (c,p1,p2) column order -> w_folded bf16 [N,Kp] = bf16(w[n,k] * gamma[k]) (fp32 product, one rounding)
+ *         with the columns permuted to (ph,pw,c) and zero padding, b_folded f32 [N] = b[n] + sum_k w[n,k] * beta[k] (fp32,
+ *         fixed order): LayerNorm_K(x) W^T + b == xhat w_folded^T + b_folded.
+ * unfold: from g f32 [N,Kp] = dPE^T xhat (columns in (ph,pw,c) order) and s f32 [N] = colsum(dPE):
+ *         dw [N,K] (f32 if dw_f32, else bf16; (c,p1,p2) order) = gamma[k] * g[n,k] + beta[k] * s[n],
+ *         dgamma f32 [K] = sum_n w[n,k] * g[n,k], dbeta f32 [K] = sum_n w[n,k] * s[n] (fp32, fixed summation order over n, no
+ *         atomics).  A null dw / dgamma / dbeta skips that output (frozen parameter).  The bias gradient is s itself. */
+int clipa_patchify_ln(const void* img, void* out, int64_t B, int64_t S, int64_t P, int64_t Kp, int in_dtype, int nhwc,
+                      int normalize, const float* mean3, const float* std3, float eps, void* stream);
+int clipa_patchnorm_fold(const void* w, int w_f32, const float* b, const float* gamma, const float* beta, void* w_folded,
+                         float* b_folded, int64_t N, int64_t P, int64_t Kp, void* stream);
+int clipa_patchnorm_unfold(const float* g, const float* s, const void* w, int w_f32, const float* gamma, const float* beta,
+                           void* dw, int dw_f32, float* dgamma, float* dbeta, int64_t N, int64_t P, int64_t Kp, void* stream);
 /* out = act(in) elementwise, bf16 (MLP activation re-materialised from the kept pre-activation) */
 int clipa_activation_fwd(const void* in, void* out, int64_t n, int act, void* stream);
 /* Fused similarity + cross-entropy of the InfoNCE loss (loss.py:128-155): logits = s * rows . cols^T (rows [R,E],
