@@ -5,15 +5,22 @@ LDS-DMA, fragment registers not re-loaded before their last use), and (3) the cr
 no scratch, no compiler-generated access to an accumulation register, 512 registers per wave."""
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from .device_asm import audited_asm, needs_hipcc
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+
+
+def positions(lines, rd="ds_read"):
+    """Line indices by kind: MFMAs, fragment reads (instruction `rd`), LDS-DMA, M0 writes, barriers, vmcnt / lgkmcnt waits,
+    slot flips of the read addresses."""
+    kinds = dict(mfma="v_mfma", rd=rd, dma="buffer_load", m0="s_add_u32 m0", vm="s_waitcnt vmcnt", lgk="s_waitcnt lgkmcnt", flip="v_xor_b32")
+    pos = {k: [i for i, l in enumerate(lines) if l.startswith(prefix)] for k, prefix in kinds.items()}
+    pos["bar"] = [i for i, l in enumerate(lines) if l == "s_barrier"]
+    return pos
 
 
 def test_inc_is_up_to_date():
@@ -28,13 +35,7 @@ def test_schedule_ordering_rules(sched):
     import gen_gemm_nta as G
     S = G.SCHEDULES_ALL[sched]
     lines = G.step_text(S, 0, "cur", False, False, str(G.younger(S)), False)
-    pos = {k: [] for k in ("mfma", "rd", "dma", "m0", "bar", "vm", "lgk")}
-    for i, l in enumerate(lines):
-        key = ("mfma" if l.startswith("v_mfma") else "rd" if l.startswith("ds_read") else "dma" if l.startswith("buffer_load") else
-               "m0" if l.startswith("s_add_u32 m0") else "bar" if l == "s_barrier" else "vm" if l.startswith("s_waitcnt vmcnt") else
-               "lgk" if l.startswith("s_waitcnt lgkmcnt") else None)
-        if key:
-            pos[key].append(i)
+    pos = positions(lines)
     assert len(pos["mfma"]) == 128 and len(pos["rd"]) == 32 and len(pos["dma"]) == 16 and len(pos["bar"]) == 2
     rd1, rd0 = pos["rd"][:16], pos["rd"][16:]
     assert max(rd1) < pos["lgk"][0] < pos["bar"][0] < min(pos["dma"])          # slot freed (all waves) before the DMA re-fills it
@@ -55,16 +56,9 @@ def test_schedule_ordering_rules(sched):
         assert all(j > i for j in readers if j >= pos["mfma"][64])             # within a step the read precedes its k-half-1 users
 
 
-@pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="hipcc not available")
+@needs_hipcc
 def test_isa_audit(tmp_path):
-    asm = tmp_path / "gemm_nta.s"
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "clipa_amd", "csrc"), "-I",
-           os.path.join(ROOT, "include"), "-Wno-unused-result", "-ffp-contract=fast", "-S", "--cuda-device-only", "-o", str(asm),
-           os.path.join(ROOT, "clipa_amd", "csrc", "gemm_nta.hip")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    a = subprocess.run([sys.executable, os.path.join(ROOT, "clipa_amd", "isa_audit.py"), str(asm)], capture_output=True, text=True)
-    assert a.returncode == 0, a.stdout[-3000:]
+    asm = audited_asm("gemm_nta.hip", tmp_path)
     assert len(re.findall(r"\.name:\s+\S*gemm_nta_kernel", asm.read_text())) == 24      # 8 epilogue flavours (5 + the three e4m3 ones) x 3 schedules
 
 
@@ -75,12 +69,11 @@ def test_tn_schedule_ordering_rules(sched):
     import gen_gemm_tna as T
     S = T.SCHEDULES[sched]
     lines = T.step_text(S, 0, "cur", False, False, str(G.younger(S)), True)
-    idx = lambda pred: [i for i, l in enumerate(lines) if pred(l)]
-    mf = idx(lambda l: l.startswith("v_mfma") and "%[cs" not in l)
-    rd, dma, bar = idx(lambda l: l.startswith("ds_read_b64_tr_b16")), idx(lambda l: l.startswith("buffer_load")), idx(lambda l: l == "s_barrier")
-    flip, vm = idx(lambda l: l.startswith("v_xor_b32")), idx(lambda l: l.startswith("s_waitcnt vmcnt"))
+    pos = positions(lines, rd="ds_read_b64_tr_b16")
+    rd, dma, bar, flip, vm = (pos[k] for k in ("rd", "dma", "bar", "flip", "vm"))
+    mf = [i for i in pos["mfma"] if "%[cs" not in lines[i]]
     assert len(mf) == 128 and len(rd) == 64 and len(dma) == 16 and len(bar) == 2 and len(flip) == 16
-    assert len(idx(lambda l: "%[cs" in l)) == 16                                 # P^T . ones: one MFMA per P block and k-half
+    assert sum("%[cs" in l for l in lines) == 16                                 # P^T . ones: one MFMA per P block and k-half
     rd1, rd0 = rd[:32], rd[32:]
     assert max(rd1) < bar[0] < min(dma) and bar[0] < min(flip) and max(flip) < vm[0] < bar[1] < min(rd0)
     assert min(rd0) > mf[63]
@@ -88,16 +81,9 @@ def test_tn_schedule_ordering_rules(sched):
     assert lines[vm[0]] == f"s_waitcnt vmcnt({issued})"
 
 
-@pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="hipcc not available")
+@needs_hipcc
 def test_tn_isa_audit(tmp_path):
-    asm = tmp_path / "gemm_tna.s"
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "clipa_amd", "csrc"), "-I",
-           os.path.join(ROOT, "include"), "-Wno-unused-result", "-ffp-contract=fast", "-S", "--cuda-device-only", "-o", str(asm),
-           os.path.join(ROOT, "clipa_amd", "csrc", "gemm_tna.hip")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    a = subprocess.run([sys.executable, os.path.join(ROOT, "clipa_amd", "isa_audit.py"), str(asm)], capture_output=True, text=True)
-    assert a.returncode == 0, a.stdout[-3000:]
+    audited_asm("gemm_tna.hip", tmp_path)
 
 
 def test_f8a_inc_is_up_to_date():
@@ -110,9 +96,7 @@ def test_f8a_schedule_ordering_rules():
     re-loaded only after the last MFMA that reads it, and in front of the first one of the next step that does (counted waits)."""
     import gen_gemm_f8a as F
     lines = F.step_text(0, "cur", False, False, "16")
-    idx = lambda pred: [i for i, l in enumerate(lines) if pred(l)]
-    mf, rd, dma = idx(lambda l: l.startswith("v_mfma")), idx(lambda l: l.startswith("ds_read_b128")), idx(lambda l: l.startswith("buffer_load"))
-    m0, bar, vm = idx(lambda l: l.startswith("s_add_u32 m0")), idx(lambda l: l == "s_barrier"), idx(lambda l: l.startswith("s_waitcnt vmcnt"))
+    mf, rd, dma, m0, bar, vm = (positions(lines, rd="ds_read_b128")[k] for k in ("mfma", "rd", "dma", "m0", "bar", "vm"))
     assert len(mf) == 64 and len(rd) == 32 and len(dma) == 16 and len(bar) == 2 and len(vm) == 1
     own = rd[:2]                                                        # this step's own B7, read at the top
     assert max(own) < mf[0] and bar[0] < min(dma) and max(dma) < vm[0] < bar[1] < min(rd[2:])
@@ -136,16 +120,9 @@ def test_f8a_schedule_ordering_rules():
     assert len(vec) == 1 and len(pieces) == 16 and vec[0] < min(pieces)     # older than the 16 pieces: the tile's final vmcnt(16) covers it
 
 
-@pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="hipcc not available")
+@needs_hipcc
 def test_f8a_isa_audit(tmp_path):
-    asm = tmp_path / "gemm_f8a.s"
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "clipa_amd", "csrc"), "-I",
-           os.path.join(ROOT, "include"), "-Wno-unused-result", "-ffp-contract=fast", "-S", "--cuda-device-only", "-o", str(asm),
-           os.path.join(ROOT, "clipa_amd", "csrc", "gemm_f8a.hip")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    a = subprocess.run([sys.executable, os.path.join(ROOT, "clipa_amd", "isa_audit.py"), str(asm)], capture_output=True, text=True)
-    assert a.returncode == 0, a.stdout[-3000:]
+    asm = audited_asm("gemm_f8a.hip", tmp_path)
     assert len(re.findall(r"\.name:\s+\S*gemm_f8a_kernel", asm.read_text())) == 24      # 12 epilogue flavours (5 + the two e4m3 pre-activation ones + 4 with a producer-quantised output + the operand-emitting GELU-backward) x e4m3 / e5m2 A operand
 
 
@@ -203,10 +180,7 @@ def test_tn8_schedule_ordering_rules(sched):
     prev = T8.step_items(S, 0, "cur", False, False, k)
     cur = T8.step_items(S, 1, "cur", False, False, k)
     lines = T8.resolve(prev, cur)
-    idx = lambda pred: [i for i, l in enumerate(lines) if pred(l)]
-    mf, rd = idx(lambda l: l.startswith("v_mfma")), idx(lambda l: l.startswith("ds_read_b64_tr_b8"))
-    dma, m0 = idx(lambda l: l.startswith("buffer_load")), idx(lambda l: l.startswith("s_add_u32 m0"))
-    bar, vm, flip = idx(lambda l: l == "s_barrier"), idx(lambda l: l.startswith("s_waitcnt vmcnt")), idx(lambda l: l.startswith("v_xor_b32"))
+    mf, rd, dma, m0, bar, vm, flip = (positions(lines, rd="ds_read_b64_tr_b8")[k] for k in ("mfma", "rd", "dma", "m0", "bar", "vm", "flip"))
     assert len(mf) == 64 and len(rd) == 64 and len(dma) == 16 and len(bar) == 2 and len(vm) == 1 and len(flip) == 16
     blocks = lambda l: tuple(int(x) for x in re.findall(r"v\[(\d+):\d+\]", l)[:2])
     pairs = {blocks(lines[i]) for i in mf}
@@ -252,14 +226,7 @@ def test_tn8_schedule_ordering_rules(sched):
     assert sum(l.startswith("ds_read_b64_tr_b8") for l in last) == 4 * T and sum(l == "s_barrier" for l in last) == 1
 
 
-@pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="hipcc not available")
+@needs_hipcc
 def test_tn8_isa_audit(tmp_path):
-    asm = tmp_path / "gemm_tn8.s"
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "clipa_amd", "csrc"), "-I",
-           os.path.join(ROOT, "include"), "-Wno-unused-result", "-ffp-contract=fast", "-S", "--cuda-device-only", "-o", str(asm),
-           os.path.join(ROOT, "clipa_amd", "csrc", "gemm_tn8.hip")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    a = subprocess.run([sys.executable, os.path.join(ROOT, "clipa_amd", "isa_audit.py"), str(asm)], capture_output=True, text=True)
-    assert a.returncode == 0, a.stdout[-3000:]
+    asm = audited_asm("gemm_tn8.hip", tmp_path)
     assert len(re.findall(r"\.name:\s+\S*gemm_tn8_kernel", asm.read_text())) == 6      # 3 schedules x e4m3 / e5m2 gradient operand

@@ -29,22 +29,12 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gen_gemm_nta import SLOT, IMG, PIECE, BLOCK, VOFF_A, VOFF_B, VADDR_A, VADDR_B, c_string, clobbers, setup_text, prologue_text  # noqa: E402
+from gemm_gen import (BLOCK, NT_DMA, VADDR_A, VADDR_B, VOFF_A, acc, blk, c_string, clobbers, define, header, main,  # noqa: E402
+                      nt_prologue_text, nt_setup_text, out_path, tile_scaffold)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "clipa_amd", "csrc", "gemm_f8a_asm.inc")
-
+OUT = out_path("f8a")
 FA, FB = 128, 192
 BAR1, DMA0, PUBLISH = 8, 9, 42
-
-
-def acc(bj, ai):
-    b = 4 * (8 * bj + ai)
-    return f"a[{b}:{b + 3}]"
-
-
-def blk(base, i):
-    return f"v[{base + 8 * i}:{base + 8 * i + 7}]"
 
 
 def reads(kind, b, slot):
@@ -67,14 +57,7 @@ def step_text(slot, srd, first, last, vmcnt):
         # the tile's vectors: one 1 KiB LDS-DMA per wave (a 0-byte descriptor for wave 3), OLDER than the step's 16 pieces
         fill[BAR1 - 2].append("s_mov_b32 m0, %[ldsv]")
         fill[BAR1 - 1].append("buffer_load_dwordx4 %[vvec], %[srdVec], 0 offen lds")
-    for q in range(16):
-        img, j = q // 8, q % 8
-        voff = (VOFF_B if img else VOFF_A) + j
-        s = "A" if img == 0 else "B"
-        fill[DMA0 + 2 * q].append(f"s_add_u32 m0, %[ldsw], {slot * SLOT + img * IMG + j * PIECE}")
-        fill[DMA0 + 2 * q + 1].append(f"buffer_load_dwordx4 v{voff}, %[{srd}{s}], %[sk] offen lds")
-    assert DMA0 + 2 * 15 + 1 < PUBLISH - 1
-    fill[PUBLISH - 1].append("s_add_u32 %[sk], %[sk], 128")
+    NT_DMA.place(fill, DMA0, 2, slot, srd, advance_at=PUBLISH - 1)
     if not last:
         fill[PUBLISH] += [f"s_waitcnt vmcnt({vmcnt})", "s_barrier"]
         for bj in range(5):
@@ -94,67 +77,34 @@ def step_text(slot, srd, first, last, vmcnt):
 
 
 def tile_text():
-    t = setup_text()
+    t = nt_setup_text()
     t.append("s_mov_b32 %[sk], 256")
-    t += ["s_waitcnt vmcnt(@VMS@)", "s_barrier"]
+    t += ["s_waitcnt vmcnt(@#VMS@)", "s_barrier"]
     for bj in range(7):
         t += reads("B", bj, 0)
     for ai in range(8):
         t += reads("A", ai, 0)
     t.append("s_waitcnt lgkmcnt(0)")
-    t += step_text(0, "cur", True, False, "@VM0@")
-    t += step_text(1, "cur", False, False, "16")
-    t += ["s_cmp_eq_u32 %[nloop], 0", "s_cbranch_scc1 F8A_TAIL_%=", "s_mov_b32 %[cnt], %[nloop]", "F8A_LOOP_%=:"]
-    t += step_text(0, "cur", False, False, "16")
-    t += step_text(1, "cur", False, False, "16")
-    t += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cmp_lg_u32 %[cnt], 0", "s_cbranch_scc1 F8A_LOOP_%=", "F8A_TAIL_%=:",
-          "s_mov_b32 %[sk], 0"]
-    t += step_text(0, "nxt", False, False, "16")
-    t += step_text(1, "nxt", False, True, None)
-    # the vectors are older than the 16 LDS-DMA of the last step; the barrier makes every wave's vector visible to the epilogue;
-    # MFMA results must be readable by v_accvgpr_read afterwards
-    t += ["s_waitcnt vmcnt(16)", "s_barrier", "s_nop 7", "s_nop 7"]
-    return t
-
-
-def c_string3(lines, indent="  "):
-    """c_string with a third stringified macro argument: the format suffix of the MFMAs."""
-    out = []
-    for l in lines:
-        if "@FMT@" in l:
-            a, b = l.split("@FMT@")
-            out.append(f'{indent}"{a}" FMT "{b}\\n\\t"')
-        else:
-            out.append(c_string([l], indent))
-    return "\n".join(out)
+    steady = [step_text(slot, "cur", False, False, "16") for slot in (0, 1)]
+    steps = [step_text(0, "cur", True, False, "@#VM0@"), steady[1]] + steady
+    steps += [step_text(0, "nxt", False, False, "16"), step_text(1, "nxt", False, True, None)]
+    # the vectors are older than the 16 LDS-DMA of the last step; the barrier makes every wave's vector visible to the epilogue
+    return t + tile_scaffold("F8A", steps, ["s_mov_b32 %[sk], 0"], ["s_waitcnt vmcnt(16)", "s_barrier"])
 
 
 def render():
-    p = ["// GENERATED by tools/gen_gemm_f8a.py - do not edit (tests/test_gemm_nta_gen_cpu.py compares it with the generator).",
-         "// Main loop of gemm_f8a_kernel as inline-asm text; register map, pipeline and schedule: see the generator's docstring.",
-         "#pragma once", "",
-         "#define F8A_PROLOGUE_ASM \\"]
-    p.append(" \\\n".join(c_string(prologue_text()).split("\n")))
-    p.append("")
+    p = header("f8a") + define("F8A_PROLOGUE_ASM", c_string(nt_prologue_text()))
     p.append("// VMS: wait in front of the tile's first fragment reads (16 + stores the epilogue before it may leave in flight);")
     p.append("// VM0: publish wait of the tile's first step (likewise).  FMT: a string, the format suffix of the MFMAs (\" cbsz:1\" ...).")
     p.append("#define F8A_TILE_ASM(S, FMT) F8A_TILE_ASM_I(F8A_VM_##S, F8A_VM_##S, FMT)")
     p.append("#define F8A_TILE_ASM_I(VMS, VM0, FMT) F8A_TILE_ASM_II(VMS, VM0, FMT)")
-    p.append("#define F8A_TILE_ASM_II(VMS, VM0, FMT) \\")
-    p.append(" \\\n".join(c_string3(tile_text()).split("\n")))
-    p.append("")
+    p += define("F8A_TILE_ASM_II(VMS, VM0, FMT)", c_string(tile_text()))
     for st in (0, 32, 64):
         p.append(f"#define F8A_VM_{st} {min(63, 16 + st)}")
     p.append("")
-    p.append("#define F8A_CLOBBERS \\")
-    p.append(" \\\n".join(clobbers().split("\n")))
-    p.append("")
+    p += define("F8A_CLOBBERS", clobbers(VOFF_A))
     return "\n".join(p)
 
 
 if __name__ == "__main__":
-    text = render()
-    if "--check" in sys.argv:
-        sys.exit(0 if open(OUT).read() == text else 1)
-    open(OUT, "w").write(text)
-    print("wrote", OUT, len(text.splitlines()), "lines")
+    main(OUT, render)

@@ -5,7 +5,8 @@
 
 Why a generator: the K loop of the 4-wave / 512-register bf16 GEMM is ONE inline-asm statement per output tile (every
 issue slot placed by hand: 128 MFMAs, 32 fragment reads, 16 LDS-DMA, 2 barriers and 3 waits per K step); writing ~1500
-lines of it by hand is how schedules rot.  The schedule is data (`SCHEDULES`), the text is derived.
+lines of it by hand is how schedules rot.  The schedule is data (`SCHEDULES`), the text is derived; what the text has in
+common with the three sibling kernels' (LDS-DMA issue, tile scaffold, rendering as a macro) is derived in tools/gemm_gen.py.
 
 Structure of one tile (256 x 256 outputs, K = 64 * nkt, nkt even >= 4; wave (wm, wn) owns 128 x 128 = 8 x 8 blocks of 16 x 16):
 
@@ -29,13 +30,12 @@ Structure of one tile (256 x 256 outputs, K = 64 * nkt, nkt even >= 4; wave (wm,
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "clipa_amd", "csrc", "gemm_nta_asm.inc")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from gemm_gen import (BLOCK, NT_DMA, VADDR_A, VADDR_B, VOFF_A, acc, c_string, clobbers, define, header, main, nt_prologue_text,  # noqa: E402
+                      nt_setup_text, out_path, tile_scaffold, vr, younger)
 
+OUT = out_path("nta")
 A0, A1, B0, B1 = 128, 160, 192, 224          # fragment register bases
-VOFF_A, VOFF_B = 96, 104                     # LDS-DMA per-lane offsets
-VADDR_A, VADDR_B = 112, 116                  # + 2 * slot + khalf
-SLOT, IMG, PIECE, BLOCK = 65536, 32768, 4096, 2048
 
 # schedule = issue slots (index of the MFMA after which the instruction is placed; 0..127) of everything that is not an MFMA
 SCHEDULES_ALL = {
@@ -60,20 +60,6 @@ SCHEDULES_ALL = {
 
 # the schedules compiled into the library (the rest were A/B'd on hardware: profiles/r03_gemm_nta_schedules_*.jsonl)
 SCHEDULES = {k: SCHEDULES_ALL[k] for k in (0, 3, 4)}
-
-
-def younger(S):
-    """LDS-DMA of a step issued before its publish wait (the wait sits after MFMA `vmwait`, DMA q after MFMA dma_start + 1 + q stride)."""
-    return sum(1 for q in range(16) if S["dma_start"] + 1 + q * S["dma_stride"] <= S["vmwait"])
-
-
-def acc(bj, ai):
-    b = 4 * (8 * bj + ai)
-    return f"a[{b}:{b + 3}]"
-
-
-def vr(base, i):
-    return f"v[{base + 4 * i}:{base + 4 * i + 3}]"
 
 
 def step_text(S, slot, srd, first, last, vmcnt, bias):
@@ -101,19 +87,10 @@ def step_text(S, slot, srd, first, last, vmcnt, bias):
         for p in range(4):
             for h in range(2):
                 fill[m - 1 - (p * 2 + h)].append(f"buffer_load_dwordx4 %[bias{p * 2 + h}], %[vbias], %[srdBias], 0 offen offset:{p * 128 + h * 16}")
-    for q in range(16):
-        img, j = q // 8, q % 8
-        voff = (VOFF_B if img else VOFF_A) + j
-        s = "A" if img == 0 else "B"
-        fill[m].append(f"s_add_u32 m0, %[ldsw], {slot * SLOT + img * IMG + j * PIECE}")
-        fill[m + 1].append(f"buffer_load_dwordx4 v{voff}, %[{srd}{s}], %[sk] offen lds")
-        m += S["dma_stride"]
-    last_dma = m - S["dma_stride"] + 1
-    assert last_dma + 1 < 127
-    fill[last_dma + 1].append("s_add_u32 %[sk], %[sk], 128")
+    NT_DMA.place(fill, m, S["dma_stride"], slot, srd)
     if not last:
         # step + 1's operands are older than everything this step has issued so far: `younger(S)` LDS-DMA may stay in flight
-        assert vmcnt in ("@VM0@", str(younger(S)))
+        assert vmcnt in ("@#VM0@", str(younger(S)))
         fill[S["vmwait"]] += [f"s_waitcnt vmcnt({vmcnt})", "s_barrier"]
         m = S["rd0_start"]
         for kind, b in order:
@@ -133,93 +110,26 @@ def step_text(S, slot, srd, first, last, vmcnt, bias):
     return lines
 
 
-def setup_text():
-    """Per-lane addresses from the four "v" inputs (recomputed per statement: nothing of ours lives in registers the
-    compiler may touch between statements except the accumulators)."""
-    t = ["s_nop 4",
-         f"v_mov_b32 v{VADDR_A}, %[va]", f"v_xor_b32 v{VADDR_A + 1}, 64, v{VADDR_A}",
-         f"v_add_u32 v{VADDR_A + 2}, 0x10000, v{VADDR_A}", f"v_add_u32 v{VADDR_A + 3}, 0x10000, v{VADDR_A + 1}",
-         f"v_mov_b32 v{VADDR_B}, %[vb]", f"v_xor_b32 v{VADDR_B + 1}, 64, v{VADDR_B}",
-         f"v_add_u32 v{VADDR_B + 2}, 0x10000, v{VADDR_B}", f"v_add_u32 v{VADDR_B + 3}, 0x10000, v{VADDR_B + 1}",
-         f"v_mov_b32 v{VOFF_A}, %[voffA]", f"v_mov_b32 v{VOFF_B}, %[voffB]"]
-    for j in range(1, 8):
-        t.append(f"v_add_u32 v{VOFF_A + j}, %[sA32], v{VOFF_A + j - 1}")
-        t.append(f"v_add_u32 v{VOFF_B + j}, %[sB32], v{VOFF_B + j - 1}")
-    return t
-
-
-def prologue_text():
-    """Very first tile of a workgroup: fetch its K steps 0 and 1 (32 LDS-DMA per wave)."""
-    t = setup_text()
-    for step in range(2):
-        t.append(f"s_mov_b32 %[sk], {step * 128}")
-        for q in range(16):
-            img, j = q // 8, q % 8
-            voff = (VOFF_B if img else VOFF_A) + j
-            s = "A" if img == 0 else "B"
-            t.append(f"s_add_u32 m0, %[ldsw], {step * SLOT + img * IMG + j * PIECE}")
-            t.append("s_nop 0")
-            t.append(f"buffer_load_dwordx4 v{voff}, %[cur{s}], %[sk] offen lds")
-    return t
-
-
 def tile_text(S):
     order = [("B", b) for b in range(8)] + [("A", a) for a in range(8)]
-    t = setup_text()
+    t = nt_setup_text()
     t.append("s_mov_b32 %[sk], 256")
     # this tile's step 0 has landed (younger: step 1's 16 LDS-DMA + whatever the epilogue before us left in flight)
-    t += ["s_waitcnt vmcnt(@VMS@)", "s_barrier"]
+    t += ["s_waitcnt vmcnt(@#VMS@)", "s_barrier"]
     for kind, b in order:
         base, addr = (B0, VADDR_B) if kind == "B" else (A0, VADDR_A)
         t.append(f"ds_read_b128 {vr(base, b)}, v{addr} offset:{b * BLOCK}")
     t.append("s_waitcnt lgkmcnt(0)")
-    t += step_text(S, 0, "cur", True, False, "@VM0@", False)
     k = str(younger(S))
-    t += step_text(S, 1, "cur", False, False, k, False)
-    t += ["s_cmp_eq_u32 %[nloop], 0", "s_cbranch_scc1 NTA_TAIL_%=", "s_mov_b32 %[cnt], %[nloop]", "NTA_LOOP_%=:"]
-    t += step_text(S, 0, "cur", False, False, k, False)
-    t += step_text(S, 1, "cur", False, False, k, False)
-    t += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cmp_lg_u32 %[cnt], 0", "s_cbranch_scc1 NTA_LOOP_%=", "NTA_TAIL_%=:",
-          "s_mov_b32 %[sk], 0"]
-    t += step_text(S, 0, "nxt", False, False, k, False)
-    t += step_text(S, 1, "nxt", False, True, None, True)
-    # the bias is older than the 16 LDS-DMA of the last step; MFMA results must be readable by v_accvgpr_read afterwards
-    t += ["s_waitcnt vmcnt(16)", "s_nop 7", "s_nop 7"]
-    return t
-
-
-def c_string(lines, indent="  "):
-    out = []
-    for l in lines:
-        if "@VM0@" in l or "@VMS@" in l:       # the immediates that differ per instantiation: macro arguments, stringified
-            name = "VM0" if "@VM0@" in l else "VMS"
-            a, b = l.split(f"@{name}@")
-            out.append(f'{indent}"{a}" #{name} "{b}\\n\\t"')
-        else:
-            out.append(f'{indent}"{l}\\n\\t"')
-    return "\n".join(out)
-
-
-def clobbers():
-    regs = [f"v{i}" for i in range(96, 256)] + [f"a{i}" for i in range(256)]
-    out, line = [], "  "
-    for r in regs:
-        tok = f'"{r}", '
-        if len(line) + len(tok) > 124:
-            out.append(line.rstrip())
-            line = "  "
-        line += tok
-    out.append(line.rstrip().rstrip(","))
-    return "\n".join(out)
+    steady = [step_text(S, slot, "cur", False, False, k, False) for slot in (0, 1)]
+    steps = [step_text(S, 0, "cur", True, False, "@#VM0@", False), steady[1]] + steady
+    steps += [step_text(S, 0, "nxt", False, False, k, False), step_text(S, 1, "nxt", False, True, None, True)]
+    # the bias is older than the 16 LDS-DMA of the last step
+    return t + tile_scaffold("NTA", steps, ["s_mov_b32 %[sk], 0"], ["s_waitcnt vmcnt(16)"])
 
 
 def render():
-    p = ["// GENERATED by tools/gen_gemm_nta.py - do not edit (tests/test_gemm_nta_gen_cpu.py compares it with the generator).",
-         "// Main loop of gemm_nta_kernel as inline-asm text; register map, pipeline and schedule: see the generator's docstring.",
-         "#pragma once", "",
-         "#define NTA_PROLOGUE_ASM \\"]
-    p.append(" \\\n".join(c_string(prologue_text()).split("\n")))
-    p.append("")
+    p = header("nta") + define("NTA_PROLOGUE_ASM", c_string(nt_prologue_text()))
     for v, S in SCHEDULES.items():
         k = younger(S)
         p.append(f"// schedule {v}: {S}")
@@ -229,21 +139,13 @@ def render():
         for st in (0, 32, 64):
             p.append(f"#define NTA_VM0_{v}_{st} {min(63, k + st)}")
         p.append(f"#define NTA_TILE_ASM_{v}_I(VMS, VM0) NTA_TILE_ASM_{v}_II(VMS, VM0)")
-        p.append(f"#define NTA_TILE_ASM_{v}_II(VMS, VM0) \\")
-        p.append(" \\\n".join(c_string(tile_text(S)).split("\n")))
-        p.append("")
+        p += define(f"NTA_TILE_ASM_{v}_II(VMS, VM0)", c_string(tile_text(S)))
     for st in (0, 32, 64):
         p.append(f"#define NTA_VMS_{st} {min(63, 16 + st)}")
     p.append("")
-    p.append("#define NTA_CLOBBERS \\")
-    p.append(" \\\n".join(clobbers().split("\n")))
-    p.append("")
+    p += define("NTA_CLOBBERS", clobbers(VOFF_A))
     return "\n".join(p)
 
 
 if __name__ == "__main__":
-    text = render()
-    if "--check" in sys.argv:
-        sys.exit(0 if open(OUT).read() == text else 1)
-    open(OUT, "w").write(text)
-    print("wrote", OUT, len(text.splitlines()), "lines")
+    main(OUT, render)

@@ -32,19 +32,20 @@ operands alike (which m a register byte holds is immaterial as long as P and Q a
               of step + 2, `s_waitcnt vmcnt` + barrier 2 publish step + 1.  One tile per workgroup (split-M slices, no tile edge):
               the last two steps issue their LDS-DMA through 0-byte descriptors (zeros land, counts stay uniform).
 """
+import functools
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gen_gemm_nta import SLOT, IMG, PIECE, c_string  # noqa: E402
+import gemm_gen  # noqa: E402
+from gemm_gen import Dma, acc, blk, c_string, clobbers, define, header, main, out_path, place_flip, tile_scaffold  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "clipa_amd", "csrc", "gemm_tn8_asm.inc")
-
+OUT = out_path("tn8")
 FP, FQ = 128, 192
 VOFF_P, VOFF_Q = 96, 104
 VADDR_P, VADDR_Q = 112, 120
 RD_I = 8192                         # bytes between the 32-row groups of a step (instruction offset of read i)
+DMA = Dma("PQ", (VOFF_P, VOFF_Q), ("skP", "skQ"), ["s_add_u32 %[skP], %[skP], %[sP128]", "s_add_u32 %[skQ], %[skQ], %[sQ128]"])
 
 # schedule = tail rows T + issue slots (index of the MFMA behind which the instruction is placed)
 SCHEDULES = {
@@ -57,13 +58,11 @@ SCHEDULES = {
 }
 
 
-def acc(ri, ci):
-    b = 4 * (8 * ri + ci)
-    return f"a[{b}:{b + 3}]"
+younger = functools.partial(gemm_gen.younger, key="publish")
 
 
-def blk(base, i):
-    return f"v[{base + 8 * i}:{base + 8 * i + 7}]"
+def txt(s):
+    return ("txt", s)
 
 
 def mfma_order(T):
@@ -81,11 +80,6 @@ def reads(kind, b):
     return [(f"ds_read_b64_tr_b8 v[{r + 2 * i}:{r + 2 * i + 1}], v{addr + b} offset:{i * RD_I}", (kind, b)) for i in range(4)]
 
 
-def younger(S):
-    """LDS-DMA of a step issued before its publish wait."""
-    return sum(1 for q in range(16) if S["dma_start"] + q * S["dma_stride"] + 1 <= S["publish"])
-
-
 def step_items(S, slot, srd, first, last, vmcnt):
     """One K step as a list of items: ("mfma", ri, ci, first) | ("rd", text, tag) | ("need", tag) | ("txt", text).
     `need` markers become counted lgkmcnt waits in resolve()."""
@@ -100,30 +94,16 @@ def step_items(S, slot, srd, first, last, vmcnt):
     for i, r in enumerate(late):
         (pre if i < per else fill)[0 if i < per else (i // per - 1)].append(("rd",) + r)
     assert (len(late) - 1) // per - 1 < S["bar1"]
-    fill[S["bar1"]] += [("txt", "s_waitcnt lgkmcnt(0)"), ("txt", "s_barrier")]
-    m = S["dma_start"]
-    assert m > S["bar1"]
-    for q in range(16):
-        img, j = q // 8, q % 8
-        voff = (VOFF_Q if img else VOFF_P) + j
-        s = "Q" if img else "P"
-        fill[m].append(("txt", f"s_add_u32 m0, %[ldsw], {slot * SLOT + img * IMG + j * PIECE}"))
-        fill[m + 1].append(("txt", f"buffer_load_dwordx4 v{voff}, %[{srd}{s}], %[sk{s}] offen lds"))
-        m += S["dma_stride"]
-    last_dma = m - S["dma_stride"] + 1
-    assert last_dma + 2 < 63
-    fill[last_dma + 1].append(("txt", "s_add_u32 %[skP], %[skP], %[sP128]"))
-    fill[last_dma + 2].append(("txt", "s_add_u32 %[skQ], %[skQ], %[sQ128]"))
+    fill[S["bar1"]] += [txt("s_waitcnt lgkmcnt(0)"), txt("s_barrier")]
+    assert S["dma_start"] > S["bar1"]
+    DMA.place(fill, S["dma_start"], S["dma_stride"], slot, srd, wrap=txt)
     # flip the fragment-read addresses to the other ring slot: behind the top reads, in front of the read-ahead
     f0 = max(S["bar1"] + 1, (len(late) - 1) // per)
-    for i in range(16):
-        mm = f0 + i
-        assert mm < S["publish"]
-        reg = (VADDR_P + i) if i < 8 else (VADDR_Q + i - 8)
-        fill[mm].append(("txt", f"v_xor_b32 v{reg}, 0x10000, v{reg}"))
+    last_flip = place_flip(fill, f0, 1, (VADDR_P, VADDR_Q), wrap=txt)
+    assert last_flip < S["publish"]
     if not last:
         assert S["publish"] < 8 * H + T - 1, "the publish barrier must precede the first Q read-ahead"
-        fill[S["publish"]] += [("txt", f"s_waitcnt vmcnt({vmcnt})"), ("txt", "s_barrier")]
+        fill[S["publish"]] += [txt(f"s_waitcnt vmcnt({vmcnt})"), txt("s_barrier")]
         for b in range(H):                      # early P blocks: as soon as published and dead (last MFMA of row b is 8 b + 7)
             mm = max(S["publish"] + 1 + b, 8 * b + 7)
             fill[mm] += [("rd",) + r for r in reads("P", b)]
@@ -197,14 +177,7 @@ def tile_text(S):
     t = setup_text()
     t += ["s_mov_b32 %[skP], 0", "s_mov_b32 %[skQ], 0"]
     for step in range(2):                       # the workgroup's K steps 0 and 1
-        for q in range(16):
-            img, j = q // 8, q % 8
-            voff = (VOFF_Q if img else VOFF_P) + j
-            s = "Q" if img else "P"
-            t.append(f"s_add_u32 m0, %[ldsw], {step * SLOT + img * IMG + j * PIECE}")
-            t.append("s_nop 0")
-            t.append(f"buffer_load_dwordx4 v{voff}, %[cur{s}], %[sk{s}] offen lds")
-        t += ["s_add_u32 %[skP], %[skP], %[sP128]", "s_add_u32 %[skQ], %[skQ], %[sQ128]"]
+        t += DMA.prologue(step) + DMA.advance
     t += ["s_waitcnt vmcnt(16)", "s_barrier"]
     pro = [r for b in range(H) for r in reads("P", b)] + [r for b in range(8) for r in reads("Q", b)]
     t += [r[0] for r in pro]
@@ -212,61 +185,21 @@ def tile_text(S):
     k = str(younger(S))
     steady0 = step_items(S, 0, "cur", False, False, k)
     steady1 = step_items(S, 1, "cur", False, False, k)
-    drained = [("txt", "s_waitcnt lgkmcnt(0)")]
-    t += resolve(drained, step_items(S, 0, "cur", True, False, k))
-    t += resolve(steady0, steady1)
-    t += ["s_cmp_eq_u32 %[nloop], 0", "s_cbranch_scc1 TN8_TAIL_%=", "s_mov_b32 %[cnt], %[nloop]", "TN8_LOOP_%=:"]
-    t += resolve(steady1, steady0)
-    t += resolve(steady0, steady1)
-    t += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cmp_lg_u32 %[cnt], 0", "s_cbranch_scc1 TN8_LOOP_%=", "TN8_TAIL_%=:"]
-    t += resolve(steady1, step_items(S, 0, "nul", False, False, k))
-    t += resolve(steady0, step_items(S, 1, "nul", False, True, None))
-    t += ["s_waitcnt vmcnt(0)", "s_nop 7", "s_nop 7"]
-    return t
-
-
-def c_string3(lines, indent="  "):
-    out = []
-    for l in lines:
-        if "@FMT@" in l:
-            a, b = l.split("@FMT@")
-            out.append(f'{indent}"{a}" FMT "{b}\\n\\t"')
-        else:
-            out.append(c_string([l], indent))
-    return "\n".join(out)
-
-
-def clobbers():
-    regs = [f"v{i}" for i in range(VOFF_P, 256)] + [f"a{i}" for i in range(256)]
-    out, line = [], "  "
-    for r in regs:
-        tok = f'"{r}", '
-        if len(line) + len(tok) > 124:
-            out.append(line.rstrip())
-            line = "  "
-        line += tok
-    out.append(line.rstrip().rstrip(","))
-    return "\n".join(out)
+    drained = [txt("s_waitcnt lgkmcnt(0)")]
+    steps = [resolve(drained, step_items(S, 0, "cur", True, False, k)), resolve(steady0, steady1),
+             resolve(steady1, steady0), resolve(steady0, steady1),
+             resolve(steady1, step_items(S, 0, "nul", False, False, k)), resolve(steady0, step_items(S, 1, "nul", False, True, None))]
+    return t + tile_scaffold("TN8", steps, [], ["s_waitcnt vmcnt(0)"])
 
 
 def render():
-    p = ["// GENERATED by tools/gen_gemm_tn8.py - do not edit (tests/test_gemm_nta_gen_cpu.py compares it with the generator).",
-         "// Main loop of gemm_tn8_kernel as inline-asm text; register map, pipeline and schedule: see the generator's docstring.",
-         "#pragma once", ""]
+    p = header("tn8")
     for v, S in SCHEDULES.items():
         p.append(f"// schedule {v}: {S}.  FMT: a string, the format suffix of the MFMAs (\"\" = e4m3 x e4m3, \" cbsz:1\" = e5m2 P operand).")
-        p.append(f"#define TN8_ASM_{v}(FMT) \\")
-        p.append(" \\\n".join(c_string3(tile_text(S)).split("\n")))
-        p.append("")
-    p.append("#define TN8_CLOBBERS \\")
-    p.append(" \\\n".join(clobbers().split("\n")))
-    p.append("")
+        p += define(f"TN8_ASM_{v}(FMT)", c_string(tile_text(S)))
+    p += define("TN8_CLOBBERS", clobbers(VOFF_P))
     return "\n".join(p)
 
 
 if __name__ == "__main__":
-    text = render()
-    if "--check" in sys.argv:
-        sys.exit(0 if open(OUT).read() == text else 1)
-    open(OUT, "w").write(text)
-    print("wrote", OUT, len(text.splitlines()), "lines")
+    main(OUT, render)

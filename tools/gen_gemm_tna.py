@@ -24,16 +24,15 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gen_gemm_nta import SLOT, IMG, PIECE, c_string, younger  # noqa: E402
+from gemm_gen import Dma, acc, c_string, clobbers, define, header, main, out_path, place_flip, tile_scaffold, vr, younger  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "clipa_amd", "csrc", "gemm_tna_asm.inc")
-
+OUT = out_path("tna")
 P0, P1, Q0, Q1 = 128, 160, 192, 224
 VOFF_P, VOFF_Q = 96, 104
 VADDR_P, VADDR_Q = 112, 120
 ONES = 92
 KHALF, HALF = 16384, 2048          # bytes: 32 image rows, 4 image rows
+DMA = Dma("PQ", (VOFF_P, VOFF_Q), ("skP", "skQ"), ["s_add_u32 %[skP], %[skP], %[sP64]", "s_add_u32 %[skQ], %[skQ], %[sQ64]"])
 
 SCHEDULES = {
     # reads one per MFMA (32 per phase), slot freed at MFMA 36, DMA one per four MFMAs, publish leaves the DMA issued so far in flight
@@ -41,15 +40,6 @@ SCHEDULES = {
     # two reads per MFMA slot at the front, slot freed at MFMA 20, DMA one per five MFMAs
     1: dict(rd1_start=0, rd1_stride=0.5, bar1=20, dma_start=22, dma_stride=5, vmwait=100, rd0_start=102, rd0_stride=0.75, lgk_end=127, flip_start=24),
 }
-
-
-def acc(ri, ci):
-    b = 4 * (8 * ri + ci)
-    return f"a[{b}:{b + 3}]"
-
-
-def vr(base, i):
-    return f"v[{base + 4 * i}:{base + 4 * i + 3}]"
 
 
 def frag_reads(base, addr, kk):
@@ -73,25 +63,12 @@ def step_text(S, slot, srd, first, last, vmcnt, colsum):
     fill[S["bar1"]] += ["s_waitcnt lgkmcnt(0)", "s_barrier"]
     m = S["dma_start"]
     assert m > S["bar1"]
-    for q in range(16):
-        img, j = q // 8, q % 8
-        voff = (VOFF_Q if img else VOFF_P) + j
-        s = "P" if img == 0 else "Q"
-        fill[m].append(f"s_add_u32 m0, %[ldsw], {slot * SLOT + img * IMG + j * PIECE}")
-        fill[m + 1].append(f"buffer_load_dwordx4 v{voff}, %[{srd}{s}], %[sk{s}] offen lds")
-        m += S["dma_stride"]
-    last_dma = m - S["dma_stride"] + 1
-    assert last_dma + 2 < 127
-    fill[last_dma + 1].append("s_add_u32 %[skP], %[skP], %[sP64]")
-    fill[last_dma + 2].append("s_add_u32 %[skQ], %[skQ], %[sQ64]")
+    DMA.place(fill, m, S["dma_stride"], slot, srd)
     # flip the fragment-read addresses to the other slot (after this step's reads, before the read-ahead)
-    for i in range(16):
-        m = S["flip_start"] + 2 * i + 1
-        assert S["bar1"] < m < S["vmwait"]
-        reg = (VADDR_P + i) if i < 8 else (VADDR_Q + i - 8)
-        fill[m].append(f"v_xor_b32 v{reg}, 0x10000, v{reg}")
+    last_flip = place_flip(fill, S["flip_start"] + 1, 2, (VADDR_P, VADDR_Q))
+    assert S["bar1"] < S["flip_start"] + 1 and last_flip < S["vmwait"]
     if not last:
-        assert vmcnt in ("@VM0@", str(younger(S)))
+        assert vmcnt == str(younger(S))
         fill[S["vmwait"]] += [f"s_waitcnt vmcnt({vmcnt})", "s_barrier"]
         reads = frag_reads(P0, VADDR_P, 0) + frag_reads(Q0, VADDR_Q, 0)
         for i, r in enumerate(reads):
@@ -132,63 +109,27 @@ def tile_text(S, colsum):
     # the workgroup's K steps 0 and 1
     t += ["s_mov_b32 %[skP], 0", "s_mov_b32 %[skQ], 0"]
     for step in range(2):
-        for q in range(16):
-            img, j = q // 8, q % 8
-            voff = (VOFF_Q if img else VOFF_P) + j
-            s = "P" if img == 0 else "Q"
-            t.append(f"s_add_u32 m0, %[ldsw], {step * SLOT + img * IMG + j * PIECE}")
-            t.append("s_nop 0")
-            t.append(f"buffer_load_dwordx4 v{voff}, %[cur{s}], %[sk{s}] offen lds")
-        t += ["s_add_u32 %[skP], %[skP], %[sP64]", "s_add_u32 %[skQ], %[skQ], %[sQ64]"]
+        t += DMA.prologue(step) + DMA.advance
     t += ["s_waitcnt vmcnt(16)", "s_barrier"]
     t += frag_reads(P0, VADDR_P, 0) + frag_reads(Q0, VADDR_Q, 0)
     t.append("s_waitcnt lgkmcnt(0)")
     k = str(younger(S))
-    t += step_text(S, 0, "cur", True, False, k, colsum)
-    t += step_text(S, 1, "cur", False, False, k, colsum)
-    t += ["s_cmp_eq_u32 %[nloop], 0", "s_cbranch_scc1 TNA_TAIL_%=", "s_mov_b32 %[cnt], %[nloop]", "TNA_LOOP_%=:"]
-    t += step_text(S, 0, "cur", False, False, k, colsum)
-    t += step_text(S, 1, "cur", False, False, k, colsum)
-    t += ["s_sub_u32 %[cnt], %[cnt], 1", "s_cmp_lg_u32 %[cnt], 0", "s_cbranch_scc1 TNA_LOOP_%=", "TNA_TAIL_%=:"]
+    steady = [step_text(S, slot, "cur", False, False, k, colsum) for slot in (0, 1)]
+    steps = [step_text(S, 0, "cur", True, False, k, colsum), steady[1]] + steady
     # the last two steps have nothing left to fetch: their LDS-DMA go through descriptors of 0 bytes (zeros land, counts stay uniform)
-    t += step_text(S, 0, "nul", False, False, k, colsum)
-    t += step_text(S, 1, "nul", False, True, None, colsum)
-    t += ["s_waitcnt vmcnt(0)", "s_nop 7", "s_nop 7"]
-    return t
-
-
-def clobbers():
-    regs = [f"v{i}" for i in range(ONES, 256)] + [f"a{i}" for i in range(256)]
-    out, line = [], "  "
-    for r in regs:
-        tok = f'"{r}", '
-        if len(line) + len(tok) > 124:
-            out.append(line.rstrip())
-            line = "  "
-        line += tok
-    out.append(line.rstrip().rstrip(","))
-    return "\n".join(out)
+    steps += [step_text(S, 0, "nul", False, False, k, colsum), step_text(S, 1, "nul", False, True, None, colsum)]
+    return t + tile_scaffold("TNA", steps, [], ["s_waitcnt vmcnt(0)"])
 
 
 def render():
-    p = ["// GENERATED by tools/gen_gemm_tna.py - do not edit (tests/test_gemm_nta_gen_cpu.py compares it with the generator).",
-         "// Main loop of gemm_tna_kernel as inline-asm text; register map, pipeline and schedule: see the generator's docstring.",
-         "#pragma once", ""]
+    p = header("tna")
     for v, S in SCHEDULES.items():
         for cs in (0, 1):
             p.append(f"// schedule {v}{' + column sums' if cs else ''}: {S}")
-            p.append(f"#define TNA_ASM_{v}_{cs} \\")
-            p.append(" \\\n".join(c_string(tile_text(S, bool(cs))).split("\n")))
-            p.append("")
-    p.append("#define TNA_CLOBBERS \\")
-    p.append(" \\\n".join(clobbers().split("\n")))
-    p.append("")
+            p += define(f"TNA_ASM_{v}_{cs}", c_string(tile_text(S, bool(cs))))
+    p += define("TNA_CLOBBERS", clobbers(ONES))
     return "\n".join(p)
 
 
 if __name__ == "__main__":
-    text = render()
-    if "--check" in sys.argv:
-        sys.exit(0 if open(OUT).read() == text else 1)
-    open(OUT, "w").write(text)
-    print("wrote", OUT, len(text.splitlines()), "lines")
+    main(OUT, render)
