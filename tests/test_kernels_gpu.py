@@ -4,7 +4,14 @@ CPU oracle maths (oracle/clip_oracle.py) / plain fp32 torch on the same seeded i
 Tolerances (stated per check): GEMM-type outputs are compared against an fp64-accumulated product of the
 SAME bf16 operands, so the only differences are fp32 accumulation order and the final bf16 rounding
 (<= 2^-8 relative); HBM-bound fp32 kernels are held to ~1e-5.
+
+Sections that are about ONE kernel's structure rather than an operation (search for the heading): "the persistent NT GEMMs past
+one tile per workgroup" (gemm_nta / gemm_nt2, tests/tile_walk.py) and "gemm_tna across tiles and slices" (the four-wave
+weight-gradient kernel on integer operands whose products are exact in fp32, tests/tn_plan.py).  Which kernel a launch went to
+is read from lib.last_gemm() / lib.gemm_counts(); the family codes are at `NTA, NT2, TNA = ...` below.
 """
+import ctypes
+import functools
 import math
 
 import numpy as np
@@ -13,6 +20,7 @@ import torch
 
 from oracle import clip_oracle as O
 from . import tile_walk as TW
+from . import tn_plan as TP
 
 pytestmark = pytest.mark.gpu
 bf16, f32 = torch.bfloat16, torch.float32
@@ -97,7 +105,10 @@ def _last_gemm():
     return lib.last_gemm()
 
 
-NTA, NT2, TNA = 2, 1, 5                  # kernel families reported by lib.last_gemm()
+# Kernel families as lib.last_gemm() reports them and lib.gemm_counts() indexes them (csrc/internal_hooks.h; the full list is
+# in clipa_amd/lib.py): 1 gemm_nt2, 2 gemm_nta, 3 gemm_tn2, 4 gemm_tn3, 5 gemm_tna.  The weight-gradient ones are also in
+# tests/tn_plan.py (TP.TN2, TP.TN3, TP.TNA), which restates which of them the launcher picks for a shape.
+NTA, NT2, TNA = 2, 1, 5
 
 
 @pytest.mark.parametrize("M,N,K", [(1024, 768, 512), (2304, 512, 256), (512, 1024, 1152)])
@@ -520,6 +531,236 @@ def test_gemm_tn_strided_and_many_slices():
     p, q = big[:, :R], big[:, R:]
     out = ops().gemm_tn(p, q, f32)
     check("slices", out, p.double().cpu().T @ q.double().cpu(), 2e-4, 2e-2)
+
+
+# ---- gemm_tna across tiles and slices -------------------------------------------------------------------------------------
+# The four-wave weight-gradient kernel (gemm_tna.hip) takes every whole-tile block gradient of the production configurations,
+# and test_gemm_tn_production_rows reaches it with ONE tile, a full grid and a tolerance that a dropped 64-row K step per slice
+# fits into.  Here: the smallest shapes with several tiles in both work orders, idle workgroups in the rounded-up grid, fewer
+# slices than the workspace was sized for, a short last slice, the minimal main loop (tests/tn_plan.py restates the plan and the
+# decode; test_tile_walk_cpu.py holds the case table at 256 CUs) - on operands that make every check an equality.
+def exact_operands(M, R, C, seed, guarded=False):
+    """Seeded bf16 operands with integer entries: P in [-4, 3], Q in [-3, 4], drawn independently (means -0.5 / +0.5: neither
+    the product nor the column sums centre on zero).  Every product is an integer of magnitude <= 16 and every partial sum of up
+    to 33 024 of them - per MFMA, per slice, across slices, in any order and grouping - an integer below 2^20, exactly
+    representable in fp32 even for a matrix pipe that aligns its addends to the largest and truncates (the accumulator's 24 bits
+    then still reach below 1).  So the f32 output equals the fp64 product bit for bit, the bf16 output its round-to-nearest-even
+    cast (ties are frequent: the values are integers of up to 15 bits), the column sums p.sum(0).
+
+    guarded: P and Q are column views of ONE [M + 192, R + 16 + C] buffer whose gap columns and rows from M on are NaN - a row
+    stride wider than R and C, and anything consumed from outside a tile's columns or past the last slice's rows poisons the
+    output (0 * NaN = NaN).  -> device tensors."""
+    assert 16 * M < 2 ** 20
+    g = torch.Generator().manual_seed(seed)
+    p = torch.randint(-4, 4, (M, R), generator=g).to(bf16)
+    q = torch.randint(-3, 5, (M, C), generator=g).to(bf16)
+    if not guarded:
+        return p.to(DEV), q.to(DEV)
+    buf = torch.full((M + 192, R + 16 + C), float("nan"), dtype=bf16)
+    buf[:M, :R], buf[:M, R + 16:] = p, q
+    buf = buf.to(DEV)
+    return buf[:M, :R], buf[:M, R + 16:]
+
+
+def exact_reference(p, q):
+    """fp64 product and column sums on the device (torch, none of the project's kernels) -> (ref [R, C], colsum [R]), fp64."""
+    pd = p.double()
+    return pd.T @ q.double(), pd.sum(0)
+
+
+def assert_exact(name, got, ref):
+    """got == ref element for element (fp64 `ref`; a bf16 `got` is compared with the round-to-nearest-even cast of ref - the
+    integers here are exact in fp32, so the cast through fp32 rounds once).  The message names the first element that differs."""
+    assert got.shape == ref.shape, f"{name}: shape {tuple(got.shape)} vs {tuple(ref.shape)}"
+    want = ref.float().to(bf16).double() if got.dtype == bf16 else ref
+    g = got.double()
+    if torch.equal(g, want):
+        return
+    bad = g != want                                        # NaN != anything
+    i = int(torch.nonzero(bad.reshape(-1))[0])
+    idx = tuple(int(v) for v in np.unravel_index(i, tuple(g.shape)))
+    raise AssertionError(f"{name}: {int(bad.sum())}/{g.numel()} elements differ; first at {idx}: got {g.reshape(-1)[i].item()!r} "
+                         f"exact {ref.reshape(-1)[i].item()!r}" + (f" (bf16: {want.reshape(-1)[i].item()!r})" if got.dtype == bf16 else ""))
+
+
+TN_GUARDED = ("A", "E")                   # cases whose operands are strided views between NaN columns and rows
+
+
+@functools.lru_cache(maxsize=None)
+def _tn_case(case):
+    """Operands and reference of a case, made once and never written: -> (P, Q, ref, ref_colsum) on the device."""
+    M, R, C = TP.CASES[case]
+    p, q = exact_operands(M, R, C, seed=100 + ord(case), guarded=case in TN_GUARDED)
+    return (p, q) + exact_reference(p, q)
+
+
+def _library_tn_slices(M, R, C):
+    from clipa_amd import lib
+    ns = ctypes.c_int64(-1)
+    lib.query("clipa_gemm_tn_workspace", M, R, C, ctypes.byref(ns))
+    return ns.value
+
+
+def _require_case_features(case, pl):
+    """FAIL (not skip) where the device's CU count gives a case another plan than the one it is there for (tn_plan.CASES)."""
+    M, R, C = TP.CASES[case]
+    TP.require(pl.kernel == TP.TNA, case, "the shape does not reach gemm_tna", pl)
+    TP.require(pl.tiles > 1, case, "one tile", pl)
+    if case in "ABCF":
+        TP.require(pl.per_xcd, case, "not in slice order", pl)
+    if case == "A":
+        TP.require(pl.tiles_r > 1 and pl.tiles_c > 1 and pl.nloop == 0 and pl.nslices < pl.S_plan and pl.idle == 0, case,
+                   "wants several tile rows and columns, 256-row slices and fewer slices than the workspace holds", pl)
+    if case == "B":
+        TP.require(pl.nslices % 8 != 0 and pl.idle > 0, case, "wants a slice count that is no multiple of 8: idle workgroups", pl)
+    if case == "C":
+        TP.require(pl.nloop >= 1 and pl.last_rows < pl.slice_rows and pl.idle > 0, case, "wants main-loop trips, a short last slice and idle workgroups", pl)
+    if case == "D":
+        TP.require(not pl.per_xcd and pl.tiles > 8 and pl.tiles % 8 != 0 and pl.tiles_r > 1, case, "wants the tile order with more than 8 tiles and a remainder", pl)
+    if case == "E":
+        TP.require(not pl.per_xcd and pl.tiles < 8 and pl.nloop >= 1 and pl.last_rows < pl.slice_rows, case, "wants the tile order with fewer tiles than XCDs and a short last slice", pl)
+    if case == "F":
+        TP.require(R > C and pl.nloop >= 2 and pl.nloop_last not in (0, pl.nloop) and pl.idle > 0, case, "wants R > C, a long main loop, a shorter one in the last slice and idle workgroups", pl)
+
+
+@pytest.mark.parametrize("case", list(TP.CASES))
+def test_gemm_tna_tiles_and_slices_exact(case):
+    """gemm_tna on the case shapes of tests/tn_plan.py, exact operands (exact_operands; cases A and E strided between NaN):
+      * routed to gemm_tna (last_gemm, gemm_counts), never silently to gemm_tn2 / gemm_tn3, with the library's slice count the
+        restated plan's on this device;
+      * the f32 output and the fused column sums equal the fp64 product bit for bit, the bf16 output (another instantiation of
+        the reduce) its RNE cast, the same without column sums (the main loop without the P^T . ones MFMAs in tile column 0);
+      * identical bits on a second launch and after another case's shape ran in between (other LDS contents, descriptor
+        extents and workspace layout);
+      * schedule 1 (flag 32768) bit for bit schedule 0; gemm_tn2 / gemm_tn3 (flags 2048 / 1024 / 16384) and both forced work
+        orders (4096 / 8192), on whatever kernel the restated plan predicts for them, exact as well.
+    Observed on an MI355X (256 CUs): every equality holds on all six cases - the matrix pipe, the slab reduce and the P^T . ones
+    column sums are exact on these integers, on all three kernels.  Checked once by hand against edited builds: one main-loop
+    trip fewer fails C, E, F; the reduce over S_plan instead of S_used slabs fails all six; r0 / c0 from the swapped tile
+    indices fails all six (A-C by their column sums alone); padding workgroups that store instead of returning fail B and C."""
+    from clipa_amd import lib
+    o = ops()
+    M, R, C = TP.CASES[case]
+    ncu = num_cu()
+    pl = TP.plan(M, R, C, ncu)
+    _require_case_features(case, pl)
+    P, Q, ref, ref_cs = _tn_case(case)
+    assert (P.stride(0) > R and Q.stride(0) > C) == (case in TN_GUARDED)
+    assert _library_tn_slices(M, R, C) == pl.S_plan, "the library plans another slice count than tests/tn_plan.py"
+
+    lib.gemm_counts(reset=True)
+    w, cs = o.gemm_tn(P, Q, f32, want_colsum=True)
+    counts = lib.gemm_counts()
+    assert _last_gemm() == TNA and counts[TP.TNA] == 1 and counts[TP.TN2] == counts[TP.TN3] == 0, f"case {case} did not run on gemm_tna: {counts}"
+    assert_exact(f"{case} f32", w, ref)
+    assert_exact(f"{case} column sums", cs, ref_cs)
+    wb, csb = o.gemm_tn(P, Q, bf16, want_colsum=True)
+    assert _last_gemm() == TNA
+    assert_exact(f"{case} bf16", wb, ref)
+    assert_exact(f"{case} column sums (bf16 output)", csb, ref_cs)
+    assert_exact(f"{case} f32 without column sums", o.gemm_tn(P, Q, f32), ref)
+    assert _last_gemm() == TNA
+
+    w2, cs2 = o.gemm_tn(P, Q, f32, want_colsum=True)
+    assert torch.equal(w2, w) and torch.equal(cs2, cs), "second launch differs"
+    other = "D" if pl.per_xcd else "A"                         # a shape of the other work order, other widths and slice length
+    OP, OQ, oref, _ = _tn_case(other)
+    assert_exact(f"{other} between two launches of {case}", o.gemm_tn(OP, OQ, f32), oref)
+    w3, cs3 = o.gemm_tn(P, Q, f32, want_colsum=True)
+    assert torch.equal(w3, w) and torch.equal(cs3, cs), f"launch after case {other}'s shape differs"
+    wb3, _ = o.gemm_tn(P, Q, bf16, want_colsum=True)
+    assert torch.equal(wb3, wb), f"bf16 launch after case {other}'s shape differs"
+
+    try:
+        for flags in (TP.SCHEDULE_1, TP.FORCE_TN2, TP.FORCE_TN3, TP.NO_TNA, TP.FORCE_SLICE_ORDER, TP.FORCE_TILE_ORDER):
+            _debug_set(0, flags)
+            fpl = TP.plan(M, R, C, ncu, flags)
+            assert _library_tn_slices(M, R, C) == fpl.S_plan, f"flags {flags}: slice count"
+            lib.gemm_counts(reset=True)
+            wf, csf = o.gemm_tn(P, Q, f32, want_colsum=True)
+            wfb, _ = o.gemm_tn(P, Q, bf16, want_colsum=True)
+            counts = lib.gemm_counts()
+            assert _last_gemm() == fpl.kernel and counts[fpl.kernel] == 2, f"flags {flags}: expected kernel family {fpl.kernel}, counts {counts}"
+            assert_exact(f"{case} f32 (flags {flags})", wf, ref)
+            assert_exact(f"{case} column sums (flags {flags})", csf, ref_cs)
+            assert_exact(f"{case} bf16 (flags {flags})", wfb, ref)
+            if flags == TP.SCHEDULE_1:
+                assert fpl.kernel == TP.TNA and torch.equal(wf, w) and torch.equal(csf, cs) and torch.equal(wfb, wb), "schedule 1 differs from schedule 0"
+            if flags in (TP.FORCE_TN2, TP.FORCE_TN3, TP.NO_TNA):
+                assert fpl.kernel != TP.TNA
+            if flags in (TP.FORCE_SLICE_ORDER, TP.FORCE_TILE_ORDER):
+                assert fpl.per_xcd == (flags == TP.FORCE_SLICE_ORDER)
+    finally:
+        _debug_set(0, 0)
+    assert torch.equal(o.gemm_tn(P, Q, f32), w) and _last_gemm() == TNA, "after the flags were reset"
+
+
+@pytest.mark.parametrize("case", ["C", "D"])
+def test_gemm_tna_tiles_and_slices_gaussian(case):
+    """Cases C (slice order, short last slice, idle workgroups) and D (tile order, 12 tiles) on Gaussian operands - mantissas
+    the integer operands do not exercise - whose magnitude depends on the 256-column tile (P and Q) and on the 256-row block of M
+    (P): one decade each (tile_walk.tile_factors), so a tile or a row block taken from elsewhere is wrong by a factor.  Against
+    the fp64 product at test_gemm_tn's tolerances (f32 rtol 1e-4, bf16 2^-7, atol 3e-4 sqrt(M); column sums 1e-5, 1e-4 sqrt(M)),
+    the absolute parts scaled per element by the operands' factors: sqrt(M) -> sqrt(sum of the row-block factors squared),
+    times the factors of the element's P and Q columns."""
+    o = ops()
+    M, R, C = TP.CASES[case]
+    pl = TP.plan(M, R, C, num_cu())
+    _require_case_features(case, pl)
+    g = torch.Generator().manual_seed(40 + ord(case))
+    fm, fr, fc = rows_by_tile(M, 3, 7), rows_by_tile(R, 7, 13), rows_by_tile(C, 5, 11)
+    p = (torch.randn(M, R, generator=g) * fm[:, None] * fr[None, :]).to(bf16).to(DEV)
+    q = (torch.randn(M, C, generator=g) * 0.1 * fc[None, :]).to(bf16).to(DEV)
+    ref, ref_cs = exact_reference(p, q)
+    rootm = float(fm.double().pow(2).sum().sqrt())
+    assert rootm <= math.sqrt(M)
+    fr, fc = fr.double().to(DEV), fc.double().to(DEV)
+    atol = 3e-4 * rootm * fr[:, None] * fc[None, :]
+    w, cs = o.gemm_tn(p, q, f32, want_colsum=True)
+    assert _last_gemm() == TNA
+    check_dev(f"{case} f32", w, ref, 1e-4, atol)
+    check_dev(f"{case} column sums", cs, ref_cs, 1e-5, 1e-4 * rootm * fr)
+    wb, csb = o.gemm_tn(p, q, bf16, want_colsum=True)
+    assert _last_gemm() == TNA
+    check_dev(f"{case} bf16", wb, ref, 2 ** -7, atol)
+    assert torch.equal(csb, cs)
+
+
+@pytest.mark.parametrize("M,R,C", TP.NEIGHBOURS)
+def test_gemm_tn_neighbours_of_tna_run_on_tn2_exact(M, R, C):
+    """One step outside tna_eligible from case A (a 128-row last slice, M no multiple of 128, a partial tile, 128-row slices):
+    the launcher keeps gemm_tn2, and it is exact on the integer operands too."""
+    from clipa_amd import lib
+    o = ops()
+    pl = TP.plan(M, R, C, num_cu())
+    assert pl.kernel == TP.TN2, f"{(M, R, C)} is no neighbour of gemm_tna's shapes on this part: {pl}"
+    assert _library_tn_slices(M, R, C) == pl.S_plan
+    p, q = exact_operands(M, R, C, seed=M + C)
+    ref, ref_cs = exact_reference(p, q)
+    lib.gemm_counts(reset=True)
+    w, cs = o.gemm_tn(p, q, f32, want_colsum=True)
+    wb, csb = o.gemm_tn(p, q, bf16, want_colsum=True)
+    counts = lib.gemm_counts()
+    assert _last_gemm() == TP.TN2 and counts[TP.TN2] == 2 and counts[TP.TNA] == 0, counts
+    assert_exact("f32", w, ref)
+    assert_exact("column sums", cs, ref_cs)
+    assert_exact("bf16", wb, ref)
+    assert_exact("column sums (bf16 output)", csb, ref_cs)
+
+
+@pytest.mark.parametrize("M,R,C", [(1000, 264, 136), (130, 8, 2304), (8, 16, 16)])
+def test_gemm_tn_ragged_shapes_exact(M, R, C):
+    """The ragged shapes of test_gemm_tn (a K tail, partial tiles: gemm_tn2) on the integer operands: equalities."""
+    o = ops()
+    p, q = exact_operands(M, R, C, seed=M + R)
+    ref, ref_cs = exact_reference(p, q)
+    w, cs = o.gemm_tn(p, q, f32, want_colsum=True)
+    assert _last_gemm() == TP.TN2
+    assert_exact("f32", w, ref)
+    assert_exact("column sums", cs, ref_cs)
+    wb, csb = o.gemm_tn(p, q, bf16, want_colsum=True)
+    assert_exact("bf16", wb, ref)
+    assert_exact("column sums (bf16 output)", csb, ref_cs)
 
 
 # -------------------------------------------------------------------------------------------------
