@@ -20,34 +20,16 @@
 #include "common.h"
 #include "clipa_hip.h"
 #include "attention_common.h"
-#include "internal_hooks.h"
 
 namespace {
 
 template <int NKT, int DH, bool CAUSAL>
 __global__ __launch_bounds__((64 * attn_waves<NKT, DH>()), HD<DH>::WGS) void attn_fwd_kernel(AttnArgs pin) {
-  constexpr int LP = NKT * 32, RB = HD<DH>::RB, KS = HD<DH>::KS, DT = HD<DH>::DT;
+  constexpr int LP = NKT * 32, KS = HD<DH>::KS, DT = HD<DH>::DT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int HPW = WGHeads<NKT>::HPW, WPH = attn_waves<NKT, DH>() / HPW;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave_wg = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int slot = wave_wg / WPH, wave = wave_wg % WPH;          // head slot of this wave, wave index within the head
-  char* sK = smem + slot * (2 * LP * RB);
-  char* sV = sK + LP * RB;
-  constexpr bool STAGE = fwd_stages<NKT, DH>();                  // whole-row stores through 4 KB of LDS per wave
-  char* stage = smem + HPW * (2 * LP * RB) + wave_wg * Stg<DH>::BYTES;
-  const int l31 = lane & 31, hi = lane >> 5, q16 = (lane >> 4) & 1, i16 = lane & 15;
-  const long nheads = (long)pin.B * pin.H;
-  const long head_raw = (long)blockIdx.x * HPW + slot;
-  const bool live = head_raw < nheads;                           // the last workgroup may have empty head slots
-  const long head = live ? head_raw : nheads - 1;
-  const int b = (int)(head / pin.H), h = (int)(head - (long)b * pin.H);
-  ATTN_LOCATE_SEQUENCE
-  const size_t hoff = ((size_t)row0 * p.ld_qkv + (size_t)h * DH) * 2;
-  const unsigned nrec = (unsigned)((long)(p.L - 1) * p.ld_qkv * 2 + DH * 2);
-  const __amdgpu_buffer_rsrc_t rsQ = make_rsrc(p.q + hoff, nrec);
-  const __amdgpu_buffer_rsrc_t rsK = make_rsrc(p.k + hoff, nrec);
-  const __amdgpu_buffer_rsrc_t rsV = make_rsrc(p.v + hoff, nrec);
+  // declares: WPH, lane, wave, l31 / hi / q16 / i16, Lds, img0, img1, stage, live, h, p (L = this sequence's), row0, stat0, rsQ / rsK / rsV
+  ATTN_HEAD_PROLOGUE(NKT, DH, false)
+  char *const sK = img0, *const sV = img1;                       // (Lds::STAGE: whole-row stores through 4 KB of LDS per wave)
   dma_image<DH>(rsK, sK, LP, p.ld_qkv, wave, lane, WPH);
   dma_image<DH>(rsV, sV, LP, p.ld_qkv, wave, lane, WPH);
   // the wave's first query tile rides along with the K / V DMA; each later tile is fetched while the tile
@@ -69,46 +51,27 @@ __global__ __launch_bounds__((64 * attn_waves<NKT, DH>()), HD<DH>::WGS) void att
     } else {
       load_frags<KS, DH>(rsQ, p.ld_qkv, qg, hi, fq);
     }
-    f32x16 s[NKT];
+    f32x16 s[NKT] = {};
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
       if (CAUSAL && kt > qt) continue;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks)
-        s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_direct<DH>(sK, 32 * kt, l31, hi, ks), fq[ks], s[kt], 0, 0, 0);
+      ATTN_SCORE_TILE(s[kt], sK, 32 * kt, fq)
       if (!CAUSAL && (kt & 1)) __builtin_amdgcn_sched_barrier(0);   // keep the K-fragment reads of later tiles from piling up in registers
     }
     float inv, m2;
     softmax_rows<NKT, CAUSAL>(s, p, qt, qg, hi, inv, m2);
 
-    f32x16 o[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+    f32x16 o[DT] = {};
 #pragma unroll
     for (int kt = 0; kt < NKT; ++kt) {
       if (CAUSAL && kt > qt) continue;
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        float pv[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) pv[e] = s[kt][8 * s2 + e];
-        const bf16x8 pf = pack_frag(pv);
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_trans<DH>(sV, 32 * kt + 16 * s2, 32 * dt, hi, q16, i16), pf, o[dt], 0, 0, 0);
-      }
+      ATTN_ACC_TRANS(o, sV, 32 * kt, pack_frag(s[kt], s2))
     }
-    if constexpr (STAGE) {
+    if constexpr (Lds::STAGE) {
       if (live) store_tile<DH>(stage, p.o, p.ld_o, row0 + 32 * qt, p.L - 32 * qt, h * DH, lane, o, inv);
       if (qg < p.L && live && p.stats && hi == 0) *(float2*)(p.stats + (stat0 + qg) * 2) = make_float2(m2, inv);
     } else if (qg < p.L && live) {
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
-        store_frag_T(p.o, p.ld_o, row0 + qg, h * DH + 32 * dt, hi, o[dt], inv, DH - 32 * dt);
+      ATTN_STORE_ROWS(p.o, p.ld_o, row0 + qg, o, inv)
       if (p.stats && hi == 0) *(float2*)(p.stats + (stat0 + qg) * 2) = make_float2(m2, inv);
     }
   }
@@ -121,39 +84,24 @@ __global__ __launch_bounds__((64 * attn_waves<NKT, DH>()), HD<DH>::WGS) void att
 // (A software-pipelined variant - next pair's score MFMAs / previous pair's dK,dV MFMAs issued ahead of the softmax-gradient
 // arithmetic, bit-identical results - measured 2-14 % SLOWER on every production shape and was dropped:
 // profiles/r02_attention_bwd_pipelining_ab.jsonl.  The kernel moves ~13 GB per launch; it is not issue-bound.)
+// (Its zero-fills and its mask test stay spelled out where the other kernels write `= {}` and key_limit / key_valid: hipcc
+// schedules this kernel at the edge of the register file, and each of those forms changes its instruction stream; the
+// ATTN_* macros expand to the statements it had - profiles/attention_shared_isa.md.)
 template <int NKT, int DH, bool CAUSAL>
 __global__ __launch_bounds__((64 * attn_waves<NKT, DH>()), HD<DH>::WGS) void attn_bwd_kernel(AttnArgs pin) {
-  constexpr int LP = NKT * 32, RB = HD<DH>::RB, KS = HD<DH>::KS, DT = HD<DH>::DT;
+  constexpr int LP = NKT * 32, KS = HD<DH>::KS, DT = HD<DH>::DT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int HPW = WGHeads<NKT>::HPW, WPH = attn_waves<NKT, DH>() / HPW;
   // The eight-wave head-dim-80 instantiations fence hipcc's scheduler between the score MFMAs, the softmax-gradient arithmetic
   // and the output MFMAs of a pair: left alone it hoists the next group's LDS reads across them and runs 9 % slower
   // (profiles/r03_attention_bwd_sched_barrier_ab.jsonl; at head dim 64 the same fences move +-2 %, at short head-dim-80
   // sequences they cost up to 46 %: measured per instantiation, not a rule)
   constexpr bool FENCE = DH == 80 && NKT >= 5;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave_wg = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int slot = wave_wg / WPH, wave = wave_wg % WPH;
-  char* img0 = smem + slot * (2 * LP * RB + 3 * LP * 4);
-  char* img1 = img0 + LP * RB;
-  float* sM = (float*)(img0 + 2 * LP * RB);                      // m' = c rowmax + log2 rowsum per query (round 5: one exponent offset)
-  float* sD = sM + 2 * LP;                                       // D = <dO, O> per query  ([LP, 2 LP): free since the statistics folded)
-  constexpr bool STAGE = bwd_stages<NKT, DH>();                  // whole-row stores through 4 KB of LDS per wave
-  char* stage = smem + HPW * (2 * LP * RB + 3 * LP * 4) + wave_wg * Stg<DH>::BYTES;
-  const int l31 = lane & 31, hi = lane >> 5, q16 = (lane >> 4) & 1, i16 = lane & 15;
-  const long nheads = (long)pin.B * pin.H;
-  const long head_raw = (long)blockIdx.x * HPW + slot;
-  const bool live = head_raw < nheads;
-  const long head = live ? head_raw : nheads - 1;
-  const int b = (int)(head / pin.H), h = (int)(head - (long)b * pin.H);
-  ATTN_LOCATE_SEQUENCE
-  const size_t hoff = ((size_t)row0 * p.ld_qkv + (size_t)h * DH) * 2;
-  const size_t ooff = ((size_t)row0 * p.ld_o + (size_t)h * DH) * 2;
-  const unsigned nrec = (unsigned)((long)(p.L - 1) * p.ld_qkv * 2 + DH * 2);
-  const unsigned nrec_o = (unsigned)((long)(p.L - 1) * p.ld_o * 2 + DH * 2);
-  const __amdgpu_buffer_rsrc_t rsQ = make_rsrc(p.q + hoff, nrec), rsK = make_rsrc(p.k + hoff, nrec),
-                               rsV = make_rsrc(p.v + hoff, nrec), rsDO = make_rsrc(p.d_o + ooff, nrec_o),
-                               rsO = make_rsrc(p.o_in + ooff, nrec_o);
+  // declares: WPH, lane, wave, l31 / hi / q16 / i16, Lds, img0, img1, sM, sD, stage, live, h, p (L = this sequence's), row0, stat0,
+  // rsQ / rsK / rsV / rsDO / rsO
+  ATTN_HEAD_PROLOGUE(NKT, DH, true)
+  // of the prologue's names: sM[query] = m' = c rowmax + log2 rowsum (round 5: one exponent offset), sD[query] = D = <dO, O>
+  // at sM + 2 LP ([LP, 2 LP): free since the statistics folded)
+  constexpr bool STAGE = Lds::STAGE;                             // whole-row stores through 4 KB of LDS per wave
   const float c = p.scale * 1.4426950408889634f;
   const float* stats = p.stats + stat0 * 2;
 
@@ -180,16 +128,7 @@ __global__ __launch_bounds__((64 * attn_waves<NKT, DH>()), HD<DH>::WGS) void att
       const float2 st = *(const float2*)(stats + qg * 2);
       mp = st.x - __builtin_amdgcn_logf(st.y);
     }
-    float Dq = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      float a[8], o8[8];
-      unpack8(__builtin_bit_cast(u32x4, fdo[ks]), a);
-      unpack8(__builtin_bit_cast(u32x4, fo[ks]), o8);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) Dq += a[i] * o8[i];
-    }
-    Dq += __shfl_xor(Dq, 32, 64);
+    ATTN_ROW_DOT(Dq, fdo, fo)
     if (hi == 0) { sM[qg] = mp; sD[qg] = Dq; }
     const int lim2 = (CAUSAL ? min(p.L, qg + 1) : p.L) - 4 * hi;
     f32x16 dq[DT];
@@ -203,11 +142,7 @@ __global__ __launch_bounds__((64 * attn_waves<NKT, DH>()), HD<DH>::WGS) void att
       f32x16 s, dp;
 #pragma unroll
       for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_direct<DH>(img0, 32 * kt, l31, hi, ks), fq[ks], s, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_direct<DH>(img1, 32 * kt, l31, hi, ks), fdo[ks], dp, 0, 0, 0);
-      }
+      ATTN_SCORE_PAIR(s, dp, 32 * kt, fq, fdo)
       if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
       const bool full = CAUSAL ? ((32 * kt + 32 <= p.L) && kt < qt) : (kt < NKT - 1);
       float ds[16];
@@ -218,20 +153,12 @@ __global__ __launch_bounds__((64 * attn_waves<NKT, DH>()), HD<DH>::WGS) void att
         ds[r] = pe * (dp[r] - Dq);                     // (the 1 / sqrt(dh) of dS rides in the dQ / dK stores)
       }
       if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        const bf16x8 dsf = pack_frag(ds + 8 * s2);
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-          dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_trans<DH>(img0, 32 * kt + 16 * s2, 32 * dt, hi, q16, i16), dsf, dq[dt], 0, 0, 0);
-      }
+      ATTN_ACC_TRANS(dq, img0, 32 * kt, pack_frag(ds + 8 * s2))
     }
     if constexpr (STAGE) {
       if (live) store_tile<DH>(stage, p.dq, p.ld_dqkv, row0 + 32 * qt, p.L - 32 * qt, h * DH, lane, dq, p.scale);
     } else if (qg < p.L && live) {
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
-        store_frag_T(p.dq, p.ld_dqkv, row0 + qg, h * DH + 32 * dt, hi, dq[dt], p.scale, DH - 32 * dt);
+      ATTN_STORE_ROWS(p.dq, p.ld_dqkv, row0 + qg, dq, p.scale)
     }
   }
   // the wave's first key tile of phase 2 is still in the K / V images: same register layout as the row-wise global load, which
@@ -267,11 +194,7 @@ __global__ __launch_bounds__((64 * attn_waves<NKT, DH>()), HD<DH>::WGS) void att
       f32x16 s, dp;
 #pragma unroll
       for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_direct<DH>(img0, 32 * qt, l31, hi, ks), fk[ks], s, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_direct<DH>(img1, 32 * qt, l31, hi, ks), fv[ks], dp, 0, 0, 0);
-      }
+      ATTN_SCORE_PAIR(s, dp, 32 * qt, fk, fv)
       if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
       float pr[16], ds[16];
 #pragma unroll
@@ -293,16 +216,7 @@ __global__ __launch_bounds__((64 * attn_waves<NKT, DH>()), HD<DH>::WGS) void att
         }
       }
       if constexpr (FENCE) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        const bf16x8 pf = pack_frag(pr + 8 * s2);
-        const bf16x8 dsf = pack_frag(ds + 8 * s2);
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) {
-          dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_trans<DH>(img1, 32 * qt + 16 * s2, 32 * dt, hi, q16, i16), pf, dv[dt], 0, 0, 0);
-          dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_trans<DH>(img0, 32 * qt + 16 * s2, 32 * dt, hi, q16, i16), dsf, dk[dt], 0, 0, 0);
-        }
-      }
+      ATTN_ACC_TRANS2(dv, img1, pack_frag(pr + 8 * s2), dk, img0, pack_frag(ds + 8 * s2), 32 * qt)
     }
     if constexpr (STAGE) {
       if (live) {
@@ -310,11 +224,7 @@ __global__ __launch_bounds__((64 * attn_waves<NKT, DH>()), HD<DH>::WGS) void att
         store_tile<DH>(stage, p.dv, p.ld_dqkv, row0 + 32 * kt, p.L - 32 * kt, h * DH, lane, dv, 1.0f);
       }
     } else if (kg < p.L && live) {
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        store_frag_T(p.dk, p.ld_dqkv, row0 + kg, h * DH + 32 * dt, hi, dk[dt], p.scale, DH - 32 * dt);
-        store_frag_T(p.dv, p.ld_dqkv, row0 + kg, h * DH + 32 * dt, hi, dv[dt], 1.0f, DH - 32 * dt);
-      }
+      ATTN_STORE_ROWS2(p.dk, dk, p.scale, p.dv, dv, 1.0f, p.ld_dqkv, row0 + kg)
     }
   }
 }
@@ -326,8 +236,6 @@ __global__ __launch_bounds__((64 * attn_waves<NKT, DH>()), HD<DH>::WGS) void att
 // waves of the workgroup hold one 32-row tile each ("group"); the forward keeps a running (max, sum) per query row
 // and rescales its output accumulator per chunk (online softmax), the backward recomputes the probabilities from the
 // forward's final statistics exactly as the short kernels do.  Same fragments, swizzle and MFMA mapping as above.
-constexpr int LONG_CT = 8;          // 256 rows per chunk
-constexpr int LONG_LMAX = 1024;
 
 template <int DH>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t chunk_rsrc(const char* base, long ld, int row0, int L) {
@@ -338,12 +246,12 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t chunk_rsrc(const char* base, l
 
 template <int DH, bool CAUSAL>
 __global__ __launch_bounds__(256, HD<DH>::WGS) void attn_fwd_long_kernel(AttnArgs p) {
-  constexpr int CT = LONG_CT, RB = HD<DH>::RB, KS = HD<DH>::KS, DT = HD<DH>::DT;
+  constexpr int CT = LONG_CT, KS = HD<DH>::KS, DT = HD<DH>::DT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   char* sK = smem;
-  char* sV = sK + CT * 32 * RB;
+  char* sV = sK + LongLds<DH, false>::IMG;
   const int l31 = lane & 31, hi = lane >> 5, q16 = (lane >> 4) & 1, i16 = lane & 15;
   const long head = blockIdx.x;
   const int b = (int)(head / p.H), h = (int)(head - (long)b * p.H);
@@ -359,13 +267,9 @@ __global__ __launch_bounds__(256, HD<DH>::WGS) void attn_fwd_long_kernel(AttnArg
     const int qg = 32 * qt + l31;                        // rows >= L read zeros and are never stored
     bf16x8 fq[KS];
     load_frags<KS, DH>(rsQ, p.ld_qkv, qg, hi, fq);
-    const int lim2 = (CAUSAL ? min(p.L, qg + 1) : p.L) - 4 * hi;
+    const int lim2 = key_limit<CAUSAL>(p.L, qg, hi);
     float m_run = -1e30f, l_run = 0.f;
-    f32x16 o[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
+    f32x16 o[DT] = {};
     for (int kc = 0; kc < NT; kc += CT) {
       if (CAUSAL && kc > qt0 + 3) break;                 // every key of this chunk lies after every query of the group
       const int nct = min(CT, NT - kc);
@@ -374,22 +278,18 @@ __global__ __launch_bounds__(256, HD<DH>::WGS) void attn_fwd_long_kernel(AttnArg
       dma_image<DH>(chunk_rsrc<DH>(vb, p.ld_qkv, 32 * kc, p.L), sV, nct * 32, p.ld_qkv, wave, lane, 4);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      f32x16 s[CT];
+      f32x16 s[CT] = {};
       float mx = -1e30f;
 #pragma unroll
       for (int kt = 0; kt < CT; ++kt) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[kt][r] = 0.f;
         if (kt >= nct || (CAUSAL && kc + kt > qt)) continue;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-          s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_direct<DH>(sK, 32 * kt, l31, hi, ks), fq[ks], s[kt], 0, 0, 0);
+        ATTN_SCORE_TILE(s[kt], sK, 32 * kt, fq)
         const int T = kc + kt;
         const bool full = (32 * T + 32 <= p.L) && (!CAUSAL || T < qt);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           float v = s[kt][r];
-          if (!full) v = (32 * T + 8 * (r >> 2) + (r & 3) < lim2) ? v : -1e30f;
+          if (!full) v = key_valid(T, r, lim2) ? v : -1e30f;
           s[kt][r] = v;
           mx = fmaxf(mx, v);
         }
@@ -420,23 +320,12 @@ __global__ __launch_bounds__(256, HD<DH>::WGS) void attn_fwd_long_kernel(AttnArg
 #pragma unroll
       for (int kt = 0; kt < CT; ++kt) {
         if (kt >= nct || (CAUSAL && kc + kt > qt)) continue;
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          float pv[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) pv[e] = s[kt][8 * s2 + e];
-          const bf16x8 pf = pack_frag(pv);
-#pragma unroll
-          for (int dt = 0; dt < DT; ++dt)
-            o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_trans<DH>(sV, 32 * kt + 16 * s2, 32 * dt, hi, q16, i16), pf, o[dt], 0, 0, 0);
-        }
+        ATTN_ACC_TRANS(o, sV, 32 * kt, pack_frag(s[kt], s2))
       }
     }
     if (qg < p.L) {
       const float inv = 1.0f / l_run;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
-        store_frag_T(p.o, p.ld_o, (long)b * p.L + qg, h * DH + 32 * dt, hi, o[dt], inv, DH - 32 * dt);
+      ATTN_STORE_ROWS(p.o, p.ld_o, (long)b * p.L + qg, o, inv)
       if (p.stats && hi == 0) *(float2*)(p.stats + ((size_t)head * p.L + qg) * 2) = make_float2(m_run * c, inv);
     }
   }
@@ -444,13 +333,13 @@ __global__ __launch_bounds__(256, HD<DH>::WGS) void attn_fwd_long_kernel(AttnArg
 
 template <int DH, bool CAUSAL>
 __global__ __launch_bounds__(256, HD<DH>::WGS) void attn_bwd_long_kernel(AttnArgs p) {
-  constexpr int CT = LONG_CT, RB = HD<DH>::RB, KS = HD<DH>::KS, DT = HD<DH>::DT;
+  constexpr int CT = LONG_CT, KS = HD<DH>::KS, DT = HD<DH>::DT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   char* img0 = smem;
-  char* img1 = img0 + CT * 32 * RB;
-  float* sM = (float*)(img0 + 2 * CT * 32 * RB);
+  char* img1 = img0 + LongLds<DH, true>::IMG;
+  float* sM = LongLds<DH, true>::stats(smem);
   float* sL = sM + LONG_LMAX;
   float* sD = sL + LONG_LMAX;
   const int l31 = lane & 31, hi = lane >> 5, q16 = (lane >> 4) & 1, i16 = lane & 15;
@@ -475,23 +364,10 @@ __global__ __launch_bounds__(256, HD<DH>::WGS) void attn_bwd_long_kernel(AttnArg
     load_frags<KS, DH>(rsO, p.ld_o, qg, hi, fo);
     float2 st = make_float2(0.f, 0.f);                 // padded queries: inv = 0 -> P = 0
     if (qg < p.L) st = *(const float2*)(stats + qg * 2);
-    float Dq = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      float a[8], o8[8];
-      unpack8(__builtin_bit_cast(u32x4, fdo[ks]), a);
-      unpack8(__builtin_bit_cast(u32x4, fo[ks]), o8);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) Dq += a[i] * o8[i];
-    }
-    Dq += __shfl_xor(Dq, 32, 64);
+    ATTN_ROW_DOT(Dq, fdo, fo)
     if (hi == 0 && qt < NT) { sM[qg] = st.x; sL[qg] = st.y; sD[qg] = Dq; }
-    const int lim2 = (CAUSAL ? min(p.L, qg + 1) : p.L) - 4 * hi;
-    f32x16 dq[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dq[dt][r] = 0.f;
+    const int lim2 = key_limit<CAUSAL>(p.L, qg, hi);
+    f32x16 dq[DT] = {};
     for (int kc = 0; kc < NT; kc += CT) {
       if (CAUSAL && kc > qt0 + 3) break;
       const int nct = min(CT, NT - kc);
@@ -503,35 +379,21 @@ __global__ __launch_bounds__(256, HD<DH>::WGS) void attn_bwd_long_kernel(AttnArg
       for (int kt = 0; kt < nct; ++kt) {
         const int T = kc + kt;
         if (CAUSAL && T > qt) break;
-        f32x16 s, dp;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_direct<DH>(img0, 32 * kt, l31, hi, ks), fq[ks], s, 0, 0, 0);
-          dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_direct<DH>(img1, 32 * kt, l31, hi, ks), fdo[ks], dp, 0, 0, 0);
-        }
+        f32x16 s = {}, dp = {};
+        ATTN_SCORE_PAIR(s, dp, 32 * kt, fq, fdo)
         const bool full = (32 * T + 32 <= p.L) && (!CAUSAL || T < qt);
         float ds[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           float pe = __builtin_amdgcn_exp2f(fmaf(s[r], c, -st.x)) * st.y;
-          if (!full) pe = (32 * T + 8 * (r >> 2) + (r & 3) < lim2) ? pe : 0.f;
+          if (!full) pe = key_valid(T, r, lim2) ? pe : 0.f;
           ds[r] = pe * (dp[r] - Dq) * p.scale;
         }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const bf16x8 dsf = pack_frag(ds + 8 * s2);
-#pragma unroll
-          for (int dt = 0; dt < DT; ++dt)
-            dq[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_trans<DH>(img0, 32 * kt + 16 * s2, 32 * dt, hi, q16, i16), dsf, dq[dt], 0, 0, 0);
-        }
+        ATTN_ACC_TRANS(dq, img0, 32 * kt, pack_frag(ds + 8 * s2))
       }
     }
     if (qg < p.L) {
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt)
-        store_frag_T(p.dq, p.ld_dqkv, (long)b * p.L + qg, h * DH + 32 * dt, hi, dq[dt], 1.0f, DH - 32 * dt);
+      ATTN_STORE_ROWS(p.dq, p.ld_dqkv, (long)b * p.L + qg, dq, 1.0f)
     }
   }
 
@@ -543,11 +405,7 @@ __global__ __launch_bounds__(256, HD<DH>::WGS) void attn_bwd_long_kernel(AttnArg
     bf16x8 fk[KS], fv[KS];
     load_frags<KS, DH>(rsK, p.ld_qkv, kg, hi, fk);
     load_frags<KS, DH>(rsV, p.ld_qkv, kg, hi, fv);
-    f32x16 dk[DT], dv[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { dk[dt][r] = 0.f; dv[dt][r] = 0.f; }
+    f32x16 dk[DT] = {}, dv[DT] = {};
     for (int qc = 0; qc < NT; qc += CT) {
       const int nct = min(CT, NT - qc);
       if (CAUSAL && qc + nct <= kt0) continue;          // every query of the chunk lies before every key of the group
@@ -559,14 +417,8 @@ __global__ __launch_bounds__(256, HD<DH>::WGS) void attn_bwd_long_kernel(AttnArg
       for (int qi = 0; qi < nct; ++qi) {
         const int T = qc + qi;                          // global query tile
         if (CAUSAL && T < kt) continue;
-        f32x16 s, dp;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_direct<DH>(img0, 32 * qi, l31, hi, ks), fk[ks], s, 0, 0, 0);
-          dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_direct<DH>(img1, 32 * qi, l31, hi, ks), fv[ks], dp, 0, 0, 0);
-        }
+        f32x16 s = {}, dp = {};
+        ATTN_SCORE_PAIR(s, dp, 32 * qi, fk, fv)
         float pr[16], ds[16];
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
@@ -586,64 +438,40 @@ __global__ __launch_bounds__(256, HD<DH>::WGS) void attn_bwd_long_kernel(AttnArg
             ds[r] = pe * (dp[r] - dd[e]) * p.scale;
           }
         }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const bf16x8 pf = pack_frag(pr + 8 * s2);
-          const bf16x8 dsf = pack_frag(ds + 8 * s2);
-#pragma unroll
-          for (int dt = 0; dt < DT; ++dt) {
-            dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_trans<DH>(img1, 32 * qi + 16 * s2, 32 * dt, hi, q16, i16), pf, dv[dt], 0, 0, 0);
-            dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_trans<DH>(img0, 32 * qi + 16 * s2, 32 * dt, hi, q16, i16), dsf, dk[dt], 0, 0, 0);
-          }
-        }
+        ATTN_ACC_TRANS2(dv, img1, pack_frag(pr + 8 * s2), dk, img0, pack_frag(ds + 8 * s2), 32 * qi)
       }
     }
     if (kg < p.L) {
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        store_frag_T(p.dk, p.ld_dqkv, (long)b * p.L + kg, h * DH + 32 * dt, hi, dk[dt], 1.0f, DH - 32 * dt);
-        store_frag_T(p.dv, p.ld_dqkv, (long)b * p.L + kg, h * DH + 32 * dt, hi, dv[dt], 1.0f, DH - 32 * dt);
-      }
+      ATTN_STORE_ROWS2(p.dk, dk, 1.0f, p.dv, dv, 1.0f, p.ld_dqkv, (long)b * p.L + kg)
     }
   }
 }
 
-template <int NKT, int DH, bool CAUSAL>
-int launch_fwd_c(const AttnArgs& a, hipStream_t st) {
-  constexpr int HPW = WGHeads<NKT>::HPW;
-  const int lds = HPW * 2 * NKT * 32 * HD<DH>::RB + (fwd_stages<NKT, DH>() ? attn_waves<NKT, DH>() * Stg<DH>::BYTES : 0);
+template <int NKT, int DH, bool CAUSAL, bool BWD>
+int launch_short_c(const AttnArgs& a, hipStream_t st) {
+  constexpr int HPW = WGHeads<NKT>::HPW, lds = ShortLds<NKT, DH, BWD>::BYTES;
+  void (*const fn)(AttnArgs) = BWD ? attn_bwd_kernel<NKT, DH, CAUSAL> : attn_fwd_kernel<NKT, DH, CAUSAL>;
+  const char* name = BWD ? "attn_bwd" : "attn_fwd";
   // one opt-in per kernel instantiation: the LDS size differs between them
   static clipa_gemm::LdsOptIn optin;
   int dev = 0;
   if (int rc = clipa_gemm::current_device(&dev)) return rc;
-  if (int rc = optin.ensure(dev, {(const void*)attn_fwd_kernel<NKT, DH, CAUSAL>}, lds, "attn_fwd")) return rc;
-  hipLaunchKernelGGL((attn_fwd_kernel<NKT, DH, CAUSAL>), dim3((unsigned)(((long)a.B * a.H + HPW - 1) / HPW)), dim3(64 * attn_waves<NKT, DH>()), lds, st, a);
-  return clipa_check_launch("attn_fwd");
+  if (int rc = optin.ensure(dev, {(const void*)fn}, lds, name)) return rc;
+  hipLaunchKernelGGL(fn, dim3((unsigned)(((long)a.B * a.H + HPW - 1) / HPW)), dim3(64 * attn_waves<NKT, DH>()), lds, st, a);
+  return clipa_check_launch(name);
 }
 template <int NKT, int DH>
 int launch_fwd(const AttnArgs& a, hipStream_t st) {
-  return a.causal ? launch_fwd_c<NKT, DH, true>(a, st) : launch_fwd_c<NKT, DH, false>(a, st);
-}
-template <int NKT, int DH, bool CAUSAL>
-int launch_bwd_c(const AttnArgs& a, hipStream_t st) {
-  constexpr int HPW = WGHeads<NKT>::HPW;
-  const int lds = HPW * (2 * NKT * 32 * HD<DH>::RB + 3 * NKT * 32 * 4) + (bwd_stages<NKT, DH>() ? attn_waves<NKT, DH>() * Stg<DH>::BYTES : 0);
-  // one opt-in per kernel instantiation: the LDS size differs between them
-  static clipa_gemm::LdsOptIn optin;
-  int dev = 0;
-  if (int rc = clipa_gemm::current_device(&dev)) return rc;
-  if (int rc = optin.ensure(dev, {(const void*)attn_bwd_kernel<NKT, DH, CAUSAL>}, lds, "attn_bwd")) return rc;
-  hipLaunchKernelGGL((attn_bwd_kernel<NKT, DH, CAUSAL>), dim3((unsigned)(((long)a.B * a.H + HPW - 1) / HPW)), dim3(64 * attn_waves<NKT, DH>()), lds, st, a);
-  return clipa_check_launch("attn_bwd");
+  return a.causal ? launch_short_c<NKT, DH, true, false>(a, st) : launch_short_c<NKT, DH, false, false>(a, st);
 }
 template <int NKT, int DH>
 int launch_bwd(const AttnArgs& a, hipStream_t st) {
-  return a.causal ? launch_bwd_c<NKT, DH, true>(a, st) : launch_bwd_c<NKT, DH, false>(a, st);
+  return a.causal ? launch_short_c<NKT, DH, true, true>(a, st) : launch_short_c<NKT, DH, false, true>(a, st);
 }
 
 template <int DH, bool CAUSAL, bool BWD>
 int launch_long(const AttnArgs& a, hipStream_t st) {
-  const int lds = 2 * LONG_CT * 32 * HD<DH>::RB + (BWD ? 3 * LONG_LMAX * 4 : 0);
+  constexpr int lds = LongLds<DH, BWD>::BYTES;
   const void* fn = BWD ? (const void*)attn_bwd_long_kernel<DH, CAUSAL> : (const void*)attn_fwd_long_kernel<DH, CAUSAL>;
   static clipa_gemm::LdsOptIn optin;
   int dev = 0;
@@ -686,8 +514,8 @@ int check_args(int64_t B, int64_t H, int64_t L, int64_t dh, int64_t ld_qkv, int6
 #ifdef CLIPA_ATTN_WIDE
 // attention_wide.hip: the non-causal kernels of the wide heads (ViT-g/14 88, ViT-bigG/14 104, ViT-e/14 112; image towers only),
 // a translation unit of their own so that the build stays parallel.  `args` is this file's AttnArgs.
-template <int NKT, int DH> int wide_fwd(const AttnArgs& a, hipStream_t st) { return launch_fwd_c<NKT, DH, false>(a, st); }
-template <int NKT, int DH> int wide_bwd(const AttnArgs& a, hipStream_t st) { return launch_bwd_c<NKT, DH, false>(a, st); }
+template <int NKT, int DH> int wide_fwd(const AttnArgs& a, hipStream_t st) { return launch_short_c<NKT, DH, false, false>(a, st); }
+template <int NKT, int DH> int wide_bwd(const AttnArgs& a, hipStream_t st) { return launch_short_c<NKT, DH, false, true>(a, st); }
 template <int DH>
 int wide_dh(const AttnArgs& a, int bwd, hipStream_t st) {
   if (a.L > 288) return bwd ? launch_long<DH, false, true>(a, st) : launch_long<DH, false, false>(a, st);
@@ -702,65 +530,37 @@ extern "C" int clipa_attn_wide_launch(const void* args, int64_t dh, int bwd, voi
 }
 #else
 extern "C" int clipa_attn_wide_launch(const void* args, int64_t dh, int bwd, void* stream);   // attention_wide.hip
-#ifdef CLIPA_ATTN_PERSISTENT_EXPERIMENT
-// tools/probes/attention_persistent/: the single-sweep backward / persistent forward of round 5, measured slower than the
-// kernels of this file (profiles/r05_attention_persistent_single_sweep.md); a probe build links them in and selects them with
-// clipa_internal_debug_set flags 262144 (backward) / 524288 (forward)
-extern "C" int clipa_attn_bwd1_try(const void* args, int64_t dh, void* stream, int* rc);
-extern "C" int clipa_attn_fwd1_try(const void* args, int64_t dh, void* stream, int* rc);
-#endif
-
 #define ATTN_DISPATCH(fn, dh, a, st)                 \
   if ((dh) == 80) { ATTN_DISPATCH_DH(fn, 80, a, st) } \
   ATTN_DISPATCH_DH(fn, 64, a, st)
 
-extern "C" int clipa_attention_fwd(const void* q, const void* k, const void* v, void* out, float* stats,
-                                   int64_t B, int64_t H, int64_t L, int64_t dh, int64_t ld_qkv, int64_t ld_o,
-                                   float scale, int causal, void* stream) {
-  if (B * H == 0) return CLIPA_OK;
-  if (int rc = check_args(B, H, L, dh, ld_qkv, ld_o, causal)) return rc;
+namespace {
+struct BwdPtrs { const void* out; const void* d_out; void* dq; void* dk; void* dv; int64_t ld_dqkv; };
+struct SeqTable { const int32_t* start; const int32_t* len; const int32_t* ids; };
+
+// the argument block of the four entry points: the forward writes `out`, the backward (g) reads it and writes the gradients; the
+// packed launches (s) pass B = sequences of the launch and L = 32 * tiles
+AttnArgs attn_args(const void* q, const void* k, const void* v, void* out, const float* stats, int64_t B, int64_t H, int64_t L,
+                   int64_t ld_qkv, int64_t ld_o, float scale, int causal, const BwdPtrs* g, const SeqTable* s) {
   AttnArgs a = {};
   a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld_qkv = ld_qkv;
   a.o = (char*)out; a.ld_o = ld_o; a.B = (int)B; a.H = (int)H; a.L = (int)L; a.scale = scale; a.causal = causal;
-  a.stats = stats;
-  if (wide_head(dh)) return clipa_attn_wide_launch(&a, dh, 0, stream);
-  if (L > 288) return dispatch_long<false>(a, dh, (hipStream_t)stream);
-#ifdef CLIPA_ATTN_PERSISTENT_EXPERIMENT
-  int rc1 = 0;
-  if ((clipa_internal_debug_flags() & 524288) && clipa_attn_fwd1_try(&a, dh, stream, &rc1)) return rc1;
-#endif
-  ATTN_DISPATCH(launch_fwd, dh, a, (hipStream_t)stream)
+  a.stats = const_cast<float*>(stats);
+  if (g) {
+    a.o_in = (const char*)g->out; a.d_o = (const char*)g->d_out;
+    a.dq = (char*)g->dq; a.dk = (char*)g->dk; a.dv = (char*)g->dv; a.ld_dqkv = g->ld_dqkv;
+  }
+  if (s) { a.seq_start = s->start; a.seq_len = s->len; a.seq_ids = s->ids; }
+  return a;
 }
 
-extern "C" int clipa_attention_bwd(const void* q, const void* k, const void* v, const void* out,
-                                   const void* d_out, const float* stats, void* dq, void* dk, void* dv, int64_t B, int64_t H,
-                                   int64_t L, int64_t dh, int64_t ld_qkv, int64_t ld_o, int64_t ld_dqkv,
-                                   float scale, int causal, void* stream) {
-  if (B * H == 0) return CLIPA_OK;
-  if (int rc = check_args(B, H, L, dh, ld_qkv, ld_o, causal)) return rc;
-  if (ld_dqkv % 8 != 0) { clipa_set_error("attention_bwd: ld_dqkv must be a multiple of 8"); return CLIPA_ERR_ARG; }
-  if (!stats) { clipa_set_error("attention_bwd: needs the forward's softmax statistics"); return CLIPA_ERR_ARG; }
-  AttnArgs a = {};
-  a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld_qkv = ld_qkv;
-  a.o_in = (const char*)out; a.d_o = (const char*)d_out; a.ld_o = ld_o;
-  a.dq = (char*)dq; a.dk = (char*)dk; a.dv = (char*)dv; a.ld_dqkv = ld_dqkv;
-  a.B = (int)B; a.H = (int)H; a.L = (int)L; a.scale = scale; a.causal = causal;
-  a.stats = const_cast<float*>(stats);
-  if (wide_head(dh)) return clipa_attn_wide_launch(&a, dh, 1, stream);
-  if (L > 288) return dispatch_long<true>(a, dh, (hipStream_t)stream);
-#ifdef CLIPA_ATTN_PERSISTENT_EXPERIMENT
-  int rc1 = 0;
-  if ((clipa_internal_debug_flags() & 262144) && clipa_attn_bwd1_try(&a, dh, stream, &rc1)) return rc1;
-#endif
-  ATTN_DISPATCH(launch_bwd, dh, a, (hipStream_t)stream)
+// what only the backward asks of its arguments; `who` = the entry point as the error texts name it
+int bwd_args(const char* who, int64_t ld_dqkv, const float* stats) {
+  if (ld_dqkv % 8 != 0) { clipa_set_error("%s: ld_dqkv must be a multiple of 8", who); return CLIPA_ERR_ARG; }
+  if (!stats) { clipa_set_error("%s: needs the forward's softmax statistics", who); return CLIPA_ERR_ARG; }
+  return 0;
 }
-// ---- packed variable-length sequences -------------------------------------------------------------------------------------
-// The text tower's captions end at their EOT token; under the causal mask no later position can reach the pooled output
-// (model.py:251-254: x[arange, text.argmax(-1)]) or receive gradient, so the engine may run the tower on the tokens up to EOT
-// only, packed back to back in one [T, 3D] matrix.  One launch handles the `nseq` sequences listed in seq_ids (or all of
-// 0 .. nseq-1) whose lengths are <= 32 * tiles; seq_start / seq_len are indexed by sequence id.  Statistics: [T, H] pairs laid
-// out per sequence as [H][len].  Head dims 64 / 80, tiles <= 9.
-namespace {
+
 int varlen_args(const int* seq_start, const int* seq_len, int64_t nseq, int64_t tiles, int64_t dh) {
   if (!seq_start || !seq_len) { clipa_set_error("attention (varlen): seq_start / seq_len missing"); return CLIPA_ERR_ARG; }
   if (tiles < 1 || tiles > 9) { clipa_set_error("attention (varlen): tiles=%ld outside [1, 9] (sequences of up to 288 tokens)", (long)tiles); return CLIPA_ERR_ARG; }
@@ -770,6 +570,36 @@ int varlen_args(const int* seq_start, const int* seq_len, int64_t nseq, int64_t 
 }
 }  // namespace
 
+extern "C" int clipa_attention_fwd(const void* q, const void* k, const void* v, void* out, float* stats,
+                                   int64_t B, int64_t H, int64_t L, int64_t dh, int64_t ld_qkv, int64_t ld_o,
+                                   float scale, int causal, void* stream) {
+  if (B * H == 0) return CLIPA_OK;
+  if (int rc = check_args(B, H, L, dh, ld_qkv, ld_o, causal)) return rc;
+  const AttnArgs a = attn_args(q, k, v, out, stats, B, H, L, ld_qkv, ld_o, scale, causal, nullptr, nullptr);
+  if (wide_head(dh)) return clipa_attn_wide_launch(&a, dh, 0, stream);
+  if (L > 288) return dispatch_long<false>(a, dh, (hipStream_t)stream);
+  ATTN_DISPATCH(launch_fwd, dh, a, (hipStream_t)stream)
+}
+
+extern "C" int clipa_attention_bwd(const void* q, const void* k, const void* v, const void* out,
+                                   const void* d_out, const float* stats, void* dq, void* dk, void* dv, int64_t B, int64_t H,
+                                   int64_t L, int64_t dh, int64_t ld_qkv, int64_t ld_o, int64_t ld_dqkv,
+                                   float scale, int causal, void* stream) {
+  if (B * H == 0) return CLIPA_OK;
+  if (int rc = check_args(B, H, L, dh, ld_qkv, ld_o, causal)) return rc;
+  if (int rc = bwd_args("attention_bwd", ld_dqkv, stats)) return rc;
+  const BwdPtrs g = {out, d_out, dq, dk, dv, ld_dqkv};
+  const AttnArgs a = attn_args(q, k, v, nullptr, stats, B, H, L, ld_qkv, ld_o, scale, causal, &g, nullptr);
+  if (wide_head(dh)) return clipa_attn_wide_launch(&a, dh, 1, stream);
+  if (L > 288) return dispatch_long<true>(a, dh, (hipStream_t)stream);
+  ATTN_DISPATCH(launch_bwd, dh, a, (hipStream_t)stream)
+}
+// ---- packed variable-length sequences -------------------------------------------------------------------------------------
+// The text tower's captions end at their EOT token; under the causal mask no later position can reach the pooled output
+// (model.py:251-254: x[arange, text.argmax(-1)]) or receive gradient, so the engine may run the tower on the tokens up to EOT
+// only, packed back to back in one [T, 3D] matrix.  One launch handles the `nseq` sequences listed in seq_ids (or all of
+// 0 .. nseq-1) whose lengths are <= 32 * tiles; seq_start / seq_len are indexed by sequence id.  Statistics: [T, H] pairs laid
+// out per sequence as [H][len].  Head dims 64 / 80, tiles <= 9.
 extern "C" int clipa_attention_fwd_varlen(const void* q, const void* k, const void* v, void* out, float* stats,
                                           const int32_t* seq_start, const int32_t* seq_len, const int32_t* seq_ids, int64_t nseq,
                                           int64_t tiles, int64_t H, int64_t dh, int64_t ld_qkv, int64_t ld_o, float scale,
@@ -777,11 +607,8 @@ extern "C" int clipa_attention_fwd_varlen(const void* q, const void* k, const vo
   if (nseq * H == 0) return CLIPA_OK;
   if (int rc = check_args(nseq, H, 32 * tiles, dh, ld_qkv, ld_o, causal)) return rc;
   if (int rc = varlen_args(seq_start, seq_len, nseq, tiles, dh)) return rc;
-  AttnArgs a = {};
-  a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld_qkv = ld_qkv;
-  a.o = (char*)out; a.ld_o = ld_o; a.B = (int)nseq; a.H = (int)H; a.L = (int)(32 * tiles); a.scale = scale; a.causal = causal;
-  a.stats = stats;
-  a.seq_start = seq_start; a.seq_len = seq_len; a.seq_ids = seq_ids;
+  const SeqTable s = {seq_start, seq_len, seq_ids};
+  const AttnArgs a = attn_args(q, k, v, out, stats, nseq, H, 32 * tiles, ld_qkv, ld_o, scale, causal, nullptr, &s);
   ATTN_DISPATCH(launch_fwd, dh, a, (hipStream_t)stream)
 }
 
@@ -793,15 +620,10 @@ extern "C" int clipa_attention_bwd_varlen(const void* q, const void* k, const vo
   if (nseq * H == 0) return CLIPA_OK;
   if (int rc = check_args(nseq, H, 32 * tiles, dh, ld_qkv, ld_o, causal)) return rc;
   if (int rc = varlen_args(seq_start, seq_len, nseq, tiles, dh)) return rc;
-  if (ld_dqkv % 8 != 0) { clipa_set_error("attention_bwd (varlen): ld_dqkv must be a multiple of 8"); return CLIPA_ERR_ARG; }
-  if (!stats) { clipa_set_error("attention_bwd (varlen): needs the forward's softmax statistics"); return CLIPA_ERR_ARG; }
-  AttnArgs a = {};
-  a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld_qkv = ld_qkv;
-  a.o_in = (const char*)out; a.d_o = (const char*)d_out; a.ld_o = ld_o;
-  a.dq = (char*)dq; a.dk = (char*)dk; a.dv = (char*)dv; a.ld_dqkv = ld_dqkv;
-  a.B = (int)nseq; a.H = (int)H; a.L = (int)(32 * tiles); a.scale = scale; a.causal = causal;
-  a.stats = const_cast<float*>(stats);
-  a.seq_start = seq_start; a.seq_len = seq_len; a.seq_ids = seq_ids;
+  if (int rc = bwd_args("attention_bwd (varlen)", ld_dqkv, stats)) return rc;
+  const BwdPtrs g = {out, d_out, dq, dk, dv, ld_dqkv};
+  const SeqTable s = {seq_start, seq_len, seq_ids};
+  const AttnArgs a = attn_args(q, k, v, nullptr, stats, nseq, H, 32 * tiles, ld_qkv, ld_o, scale, causal, &g, &s);
   ATTN_DISPATCH(launch_bwd, dh, a, (hipStream_t)stream)
 }
 #endif   // CLIPA_ATTN_WIDE

@@ -1,6 +1,10 @@
-// Shared pieces of the fused attention kernels (attention.hip, attention_wide.hip, attention_bwd1.hip): argument block, LDS image
-// geometry per head dim, the chunk swizzle that serves direct and transposed fragment reads, LDS-DMA of a head's rows, MFMA
-// fragment loads, whole-row output stores through a per-wave LDS window, the in-register row softmax.
+// Shared pieces of the fused attention kernels (attention.hip, attention_wide.hip): argument block, LDS image geometry per head
+// dim and the LDS layout of a workgroup, the chunk swizzle that serves direct and transposed fragment reads, LDS-DMA of a head's
+// rows, MFMA fragment loads, the mask bound of a score fragment, output stores (whole rows through a per-wave LDS window, or
+// scattered), the in-register row softmax, the tile arithmetic of the four kernels (ATTN_* macros: score products, <dO, O>,
+// accumulation through transposed fragments, scattered tile output), the head prologue of the short kernels.
+// (The single-sweep persistent kernels of round 5 that once shared this header were measured slower and are gone from the tree:
+// profiles/r05_attention_persistent_single_sweep.md, sources in the git history.)
 #pragma once
 #include "common.h"
 
@@ -17,7 +21,6 @@ struct AttnArgs {
   // packed variable-length sequences (short kernels only; clipa_attention_*_varlen): sequence i of this launch is
   // seq_ids[i] (or i), its rows are [seq_start[s], seq_start[s] + seq_len[s]) of the token matrix, B = sequences of the launch
   const int* seq_start; const int* seq_len; const int* seq_ids;
-  int abl;        // timing ablations of the persistent kernels (internal_hooks.h; wrong results): 1 = no pair arithmetic, 2 = no output stores
 };
 
 // Geometry per head dim.  dh = 64 (ViT-S/B/L, every text tower): 128-byte LDS rows, 4 k-steps, 2 output tiles.
@@ -189,6 +192,12 @@ __device__ __forceinline__ void store_tile(char* stage, char* base, long ld, lon
   else store_tile80(stage, base, ld, row0, rows_valid, col0, lane, a[0], a[1], a[2], mul);
 }
 
+// Mask bound of a query row: register r of the score fragment of key tile T holds key 32 T + 8 (r >> 2) + (r & 3) + 4 hi, valid
+// iff it lies below the sequence length and, under the causal mask, at or below the query qg (the 4 hi is folded into the bound).
+template <bool CAUSAL>
+__device__ __forceinline__ int key_limit(int L, int qg, int hi) { return (CAUSAL ? min(L, qg + 1) : L) - 4 * hi; }
+__device__ __forceinline__ bool key_valid(int T, int r, int lim2) { return 32 * T + 8 * (r >> 2) + (r & 3) < lim2; }
+
 // Row softmax over the transposed score fragments of one 32-query tile.  In: raw q.k scores.  Out: s =
 // exp2(c*(s - rowmax)) (un-normalised, c = scale*log2 e folded into one FMA), inv = 1/rowsum, m2 = c*rowmax.
 // key(kt, r) = 32kt + 8(r>>2) + (r&3) + 4hi is valid iff < lim (padding / causal bound); tiles valid for
@@ -198,7 +207,7 @@ template <int NKT, bool CAUSAL>
 __device__ __forceinline__ void softmax_rows(f32x16 (&s)[NKT], const AttnArgs& p, int qt, int qg, int hi,
                                              float& inv, float& m2) {
   const float c = p.scale * 1.4426950408889634f;
-  const int lim2 = (CAUSAL ? min(p.L, qg + 1) : p.L) - 4 * hi;
+  const int lim2 = key_limit<CAUSAL>(p.L, qg, hi);
   float mx = -1e30f;
 #pragma unroll
   for (int kt = 0; kt < NKT; ++kt) {
@@ -206,7 +215,7 @@ __device__ __forceinline__ void softmax_rows(f32x16 (&s)[NKT], const AttnArgs& p
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       float v = s[kt][r];
-      if (!full) v = (32 * kt + 8 * (r >> 2) + (r & 3) < lim2) ? v : -1e30f;
+      if (!full) v = key_valid(kt, r, lim2) ? v : -1e30f;
       s[kt][r] = v;
       mx = fmaxf(mx, v);
     }
@@ -238,28 +247,133 @@ __device__ __forceinline__ void load_frags(const __amdgpu_buffer_rsrc_t rs, long
   }
 }
 
-// whole-row stores (store_tile) need 16 / 10 KB of LDS more per workgroup: taken where the workgroups per CU stay what they are
-template <int NKT, int DH>
-__host__ __device__ constexpr bool fwd_stages() {
-  return (DH == 64 || DH == 80) && (WGHeads<NKT>::HPW * 2 * NKT * 32 * HD<DH>::RB + attn_waves<NKT, DH>() * Stg<DH>::BYTES) * HD<DH>::WGS <= 160 * 1024;
-}
-template <int NKT, int DH>
-__host__ __device__ constexpr bool bwd_stages() {
-  return (DH == 64 || DH == 80) && (WGHeads<NKT>::HPW * (2 * NKT * 32 * HD<DH>::RB + 3 * NKT * 32 * 4) + attn_waves<NKT, DH>() * Stg<DH>::BYTES) * HD<DH>::WGS <= 160 * 1024;
+// half s2 of the 16 probabilities a lane holds per 32-key tile, as an MFMA operand
+__device__ __forceinline__ bf16x8 pack_frag(const f32x16& v, int s2) {
+  float pv[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) pv[e] = v[8 * s2 + e];
+  return pack_frag(pv);
 }
 
+// ---- The tile arithmetic of the four kernels, one copy each.  Macros over the kernels' own names (DH, KS, DT, l31, hi, q16, i16; h
+// for the stores), not functions: every function form tried - by value, by reference, over one or two accumulators - moves the
+// compiler's schedule of the short backward, and helpers that take an accumulator array even move kernels that do not call them
+// (profiles/attention_shared_isa.md).  A macro expands to the statements the kernels had.
+// Raw scores of the image tile at `rowbase` against the wave's own 32 rows (k-step fragments f): acc += S^T[image row][own row].
+#define ATTN_SCORE_TILE(acc, img, rowbase, f)                                                                                   \
+  _Pragma("unroll") for (int ks = 0; ks < KS; ++ks)                                                                             \
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_direct<DH>(img, rowbase, l31, hi, ks), f[ks], acc, 0, 0, 0);
+// The two products of a backward pair, k-steps interleaved: s from image 0 and fa (q.k), dp from image 1 and fb (dO.v).
+#define ATTN_SCORE_PAIR(s, dp, rowbase, fa, fb)                                                                                 \
+  _Pragma("unroll") for (int ks = 0; ks < KS; ++ks) {                                                                           \
+    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_direct<DH>(img0, rowbase, l31, hi, ks), fa[ks], s, 0, 0, 0);               \
+    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_direct<DH>(img1, rowbase, l31, hi, ks), fb[ks], dp, 0, 0, 0);             \
+  }
+// float D = <dO, O> of the lane's row, from the k-step fragments of the two (each half-wave holds half of the row)
+#define ATTN_ROW_DOT(D, fdo, fo)                                                                                                \
+  float D = 0.f;                                                                                                                \
+  _Pragma("unroll") for (int ks = 0; ks < KS; ++ks) {                                                                           \
+    float a[8], o8[8];                                                                                                          \
+    unpack8(__builtin_bit_cast(u32x4, fdo[ks]), a);                                                                             \
+    unpack8(__builtin_bit_cast(u32x4, fo[ks]), o8);                                                                             \
+    _Pragma("unroll") for (int i = 0; i < 8; ++i) D += a[i] * o8[i];                                                            \
+  }                                                                                                                             \
+  D += __shfl_xor(D, 32, 64);
+// acc^T[d][own row] += image^T[d][tile row] . P[tile row][own row] over the 32-row tile at `rowbase`: the 16 values a lane holds go
+// in as two packed halves (FRAG: the bf16x8 of half s2), the image as transposed fragments.  The second form runs two
+// accumulators interleaved (dV and dK).
+#define ATTN_TRANS_MFMA(acc, img, rowbase16, f)                                                                                 \
+  acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_trans<DH>(img, rowbase16, 32 * dt, hi, q16, i16), f, acc[dt], 0, 0, 0);
+#define ATTN_ACC_TRANS(acc, img, rowbase, FRAG)                                                                                 \
+  _Pragma("unroll") for (int s2 = 0; s2 < 2; ++s2) {                                                                            \
+    const bf16x8 fa_ = FRAG;                                                                                                    \
+    _Pragma("unroll") for (int dt = 0; dt < DT; ++dt) ATTN_TRANS_MFMA(acc, img, rowbase + 16 * s2, fa_)                         \
+  }
+#define ATTN_ACC_TRANS2(acca, imga, FRAGA, accb, imgb, FRAGB, rowbase)                                                          \
+  _Pragma("unroll") for (int s2 = 0; s2 < 2; ++s2) {                                                                            \
+    const bf16x8 fa_ = FRAGA;                                                                                                   \
+    const bf16x8 fb_ = FRAGB;                                                                                                   \
+    _Pragma("unroll") for (int dt = 0; dt < DT; ++dt) {                                                                         \
+      ATTN_TRANS_MFMA(acca, imga, rowbase + 16 * s2, fa_)                                                                       \
+      ATTN_TRANS_MFMA(accb, imgb, rowbase + 16 * s2, fb_)                                                                       \
+    }                                                                                                                           \
+  }
+// The scattered output of the lane's row `row` of a tile (two tiles interleaved in the second form): DT fragments, the last one
+// partial where the head dim is no multiple of 32.
+#define ATTN_STORE_ROWS(base, ld, row, acc, mul)                                                                                \
+  _Pragma("unroll") for (int dt = 0; dt < DT; ++dt) store_frag_T(base, ld, row, h * DH + 32 * dt, hi, acc[dt], mul, DH - 32 * dt);
+#define ATTN_STORE_ROWS2(basea, acca, mula, baseb, accb, mulb, ld, row)                                                         \
+  _Pragma("unroll") for (int dt = 0; dt < DT; ++dt) {                                                                           \
+    store_frag_T(basea, ld, row, h * DH + 32 * dt, hi, acca[dt], mula, DH - 32 * dt);                                           \
+    store_frag_T(baseb, ld, row, h * DH + 32 * dt, hi, accb[dt], mulb, DH - 32 * dt);                                           \
+  }
+
+// LDS layout of a short-kernel workgroup, stated once for the kernels' pointers, the launchers' sizes and the staging decision:
+// HPW head slots of two [LP, RB] images each (the backward appends 3 LP floats of per-query statistics to a slot), then one
+// store_tile window per wave where the instantiation stages.
+// whole-row stores (store_tile) need 16 / 10 KB of LDS more per workgroup: taken where the workgroups per CU stay what they are
+// (STAGE; tests/attention_cases.py restates it as fwd_stages / bwd_stages, the names it had as two functions)
+template <int NKT, int DH, bool BWD>
+struct ShortLds {
+  static constexpr int IMG = NKT * 32 * HD<DH>::RB, SLOT = 2 * IMG + (BWD ? 3 * NKT * 32 * 4 : 0), SLOTS = WGHeads<NKT>::HPW * SLOT;
+  static constexpr int WINDOWS = attn_waves<NKT, DH>() * Stg<DH>::BYTES;
+  static constexpr bool STAGE = (DH == 64 || DH == 80) && (SLOTS + WINDOWS) * HD<DH>::WGS <= 160 * 1024;
+  static constexpr int BYTES = SLOTS + (STAGE ? WINDOWS : 0);
+  static __device__ __forceinline__ char* image(char* smem, int slot, int i) { return smem + slot * SLOT + i * IMG; }
+  static __device__ __forceinline__ float* stats(char* smem, int slot) { return (float*)(smem + slot * SLOT + 2 * IMG); }
+  static __device__ __forceinline__ char* stage(char* smem, int wave_wg) { return smem + SLOTS + wave_wg * Stg<DH>::BYTES; }
+};
+// The long kernels: two images of LONG_CT tiles; the backward appends three rows of LONG_LMAX per-query statistics.
+constexpr int LONG_CT = 8;          // 256 rows per chunk
+constexpr int LONG_LMAX = 1024;
+template <int DH, bool BWD>
+struct LongLds {
+  static constexpr int IMG = LONG_CT * 32 * HD<DH>::RB, BYTES = 2 * IMG + (BWD ? 3 * LONG_LMAX * 4 : 0);
+  static __device__ __forceinline__ float* stats(char* smem) { return (float*)(smem + 2 * IMG); }
+};
+
+// The head prologue of the short kernels.  A workgroup serves HPW heads with WPH waves each; the last workgroup may have empty
+// head slots (live = false: they run on the last head and store nothing).  Declares, for both kernels, the wave's place in the
+// workgroup, the LDS pointers, the lane split, the head's (b, h), `p`, row0 / stat0 and the descriptors of the five operand
+// matrices; the forward leaves the backward's (sM, sD, rsDO, rsO) unused.  (A macro in the backward's statement order, not a
+// function that returns these values in a struct: that form, and already another order of these statements, changes the
+// scalar prologue of every short kernel - profiles/attention_shared_isa.md.)
 // Where the (batch, head) pair of this workgroup slot lives: fixed-length batches have sequence b at rows b * L; packed
 // variable-length launches (the text tower on the tokens up to each caption's EOT) look the sequence up.  `p` is the kernel's
 // view of the arguments with L = THIS sequence's length; statistics sit at [row0 * H + h * L + query].
-#define ATTN_LOCATE_SEQUENCE                                                     \
-  AttnArgs p = pin;                                                              \
-  long row0 = (long)b * pin.L;                                                   \
-  size_t stat0 = (size_t)head * pin.L;                                           \
-  if (pin.seq_len) {                                                             \
-    const int sid = pin.seq_ids ? pin.seq_ids[b] : b;                            \
-    p.L = pin.seq_len[sid];                                                      \
-    row0 = pin.seq_start[sid];                                                   \
-    stat0 = (size_t)row0 * pin.H + (size_t)h * p.L;                              \
-  }
+#define ATTN_HEAD_PROLOGUE(NKT, DH, BWD)                                                                              \
+  constexpr int HPW = WGHeads<NKT>::HPW, WPH = attn_waves<NKT, DH>() / HPW;                                           \
+  const int tid = threadIdx.x, lane = tid & 63;                                                                       \
+  const int wave_wg = __builtin_amdgcn_readfirstlane(tid >> 6);                                                       \
+  const int slot = wave_wg / WPH, wave = wave_wg % WPH; /* head slot of this wave, wave index within the head */      \
+  using Lds = ShortLds<NKT, DH, BWD>;                                                                                 \
+  char* img0 = Lds::image(smem, slot, 0);                                                                             \
+  char* img1 = Lds::image(smem, slot, 1);                                                                             \
+  float* sM = Lds::stats(smem, slot);                   /* the backward's per-query statistics */                     \
+  float* sD = sM + 2 * NKT * 32;                                                                                      \
+  char* stage = Lds::stage(smem, wave_wg);              /* the wave's store_tile window, where Lds::STAGE */          \
+  const int l31 = lane & 31, hi = lane >> 5, q16 = (lane >> 4) & 1, i16 = lane & 15;                                  \
+  const long nheads = (long)pin.B * pin.H;                                                                            \
+  const long head_raw = (long)blockIdx.x * HPW + slot;                                                                \
+  const bool live = head_raw < nheads;                                                                                \
+  const long head = live ? head_raw : nheads - 1;                                                                     \
+  const int b = (int)(head / pin.H), h = (int)(head - (long)b * pin.H);                                               \
+  AttnArgs p = pin;                                                                                                   \
+  long row0 = (long)b * pin.L;                                                                                        \
+  size_t stat0 = (size_t)head * pin.L;                                                                                \
+  if (pin.seq_len) {                                                                                                  \
+    const int sid = pin.seq_ids ? pin.seq_ids[b] : b;                                                                 \
+    p.L = pin.seq_len[sid];                                                                                           \
+    row0 = pin.seq_start[sid];                                                                                        \
+    stat0 = (size_t)row0 * pin.H + (size_t)h * p.L;                                                                   \
+  }                                                                                                                   \
+  /* the head's rows in the [*, ld_qkv] matrices (q, k, v) and in the [*, ld_o] ones (dO and O: the backward's) */    \
+  const size_t hoff = ((size_t)row0 * p.ld_qkv + (size_t)h * DH) * 2;                                                 \
+  const size_t ooff = ((size_t)row0 * p.ld_o + (size_t)h * DH) * 2;                                                   \
+  const unsigned nrec = (unsigned)((long)(p.L - 1) * p.ld_qkv * 2 + DH * 2);                                          \
+  const unsigned nrec_o = (unsigned)((long)(p.L - 1) * p.ld_o * 2 + DH * 2);                                          \
+  const __amdgpu_buffer_rsrc_t rsQ = make_rsrc(p.q + hoff, nrec), rsK = make_rsrc(p.k + hoff, nrec),                  \
+                               rsV = make_rsrc(p.v + hoff, nrec), rsDO = make_rsrc(p.d_o + ooff, nrec_o),             \
+                               rsO = make_rsrc(p.o_in + ooff, nrec_o);
 
 }  // namespace

@@ -15,10 +15,10 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--lib", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "clipa_amd", "lib", "libclipa_hip.so"))
 ap.add_argument("--cases", default="2048,16,80:224,256,257,288;4096,16,64:192,197,224,256,257")
 args = ap.parse_args()
+from clipa_amd.lib import SIGNATURES  # noqa: E402
 lib = ctypes.CDLL(os.path.abspath(args.lib))
-P, I64, F, I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_int
-lib.clipa_attention_fwd.argtypes = [P] * 5 + [I64] * 6 + [F, I, P]
-lib.clipa_attention_bwd.argtypes = [P] * 9 + [I64] * 7 + [F, I, P]
+for name in ("clipa_attention_fwd", "clipa_attention_bwd"):
+    getattr(lib, name).restype, getattr(lib, name).argtypes = SIGNATURES[name]
 dev = "cuda"
 st = torch.cuda.current_stream().cuda_stream
 for case in args.cases.split(";"):
