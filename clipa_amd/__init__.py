@@ -11,7 +11,9 @@ and top-k similarity search (`topk_similarity`, `classify_topk`, `zero_shot_pred
 `knn_metrics`) and the logistic-regression linear probe of Radford et al. 2021 (`fit_logreg`, `logreg_objective`,
 `sweep_l2`, `evaluate_linear_probe`, and `linear_probe.linear_probe` in the module of that name); the device-side input
 pipeline (`DeviceAugment`, `DeviceEvalTransform`, `DevicePrefetcher`) over batches of images of mixed sizes (`RaggedImages`,
-`pack_images`, `ragged_collate`, `eval_geometry`).
+`pack_images`, `ragged_collate`, `eval_geometry`); and supervised fine-tuning of the image tower (`ImageClassifier`,
+`create_classifier`, `SoftTargetCrossEntropy`, `soft_target_cross_entropy`, `DeviceMixCut`, `sample_mixcut`,
+`evaluate_classification`).
 """
 from .configs import add_model_config, get_model_config, list_models
 from .factory import (create_loss, create_model, create_model_and_transforms, get_cast_dtype, load_checkpoint)
@@ -34,5 +36,9 @@ from .zero_shot import (build_classifier, class_mean_embeddings, evaluate_zero_s
                         zero_shot_ranks)
 from . import search
 from .search import classify_topk, knn_classify, knn_metrics, retrieve_topk, topk_similarity, zero_shot_predict
+from . import finetune
+from .finetune import (DeviceMixCut, ImageClassifier, SoftTargetCrossEntropy, evaluate_classification, sample_mixcut,
+                       soft_target_cross_entropy)
+from .factory import create_classifier
 
 __version__ = "0.4.0"

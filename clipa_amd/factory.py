@@ -110,6 +110,17 @@ def create_model(
     return model
 
 
+def create_classifier(model_name_or_clip, num_classes, normalize=False, init="normal", **model_kwargs):
+    """An ImageClassifier (clipa_amd/finetune.py: the `num_classes` head of clipa_jax/models/vit.py:298-306) on the image tower
+    of a CLIP: an existing model (its `visual` is shared, so fine-tuning moves the CLIP's tower too) or a model name for
+    create_model(**model_kwargs), e.g. pretrained=<checkpoint of the pre-training run>."""
+    from .finetune import ImageClassifier
+    clip = create_model(model_name_or_clip, **model_kwargs) if isinstance(model_name_or_clip, str) else model_name_or_clip
+    if model_kwargs and clip is model_name_or_clip:
+        raise TypeError(f"create_classifier: {sorted(model_kwargs)} go with a model name, not with a built model")
+    return ImageClassifier(clip.visual, num_classes, normalize=normalize, init=init)
+
+
 def create_loss(args, model=None):
     """factory.py:262-290 (ClipLoss and DistillClipLoss branches; CoCa is out of scope), plus upstream open_clip's `--siglip`
     branch (SigLipLoss).  `model` (optional, engine extension): bind the loss to the model so that the image-feature

@@ -120,6 +120,10 @@ SIGNATURES = {
     "clipa_grad_sqnorm_multi": (_I32, [_P, _P, _I32, _I32, _P, _P, _I64, _P]),
     "clipa_clip_coef": (_I32, [_P, _F, _P, _P, _P]),
     "clipa_reduce_shards": (_I32, [_P, _P, _I64, _I32, _I32, _I32, _F, _P]),
+    # image-tower fine-tuning: batch Mixup / CutMix, clipa_jax/transforms/mixup.py:141-201 (csrc/mixcut.hip), and the soft-target
+    # cross-entropy of losses/common.py:104-109 on the labels of mixup.py:203-211 (csrc/softce.hip)
+    "clipa_mixcut_u8": (_I32, [_P, _P, _P, _I64, _I64, _I32, _I32, _P, _P]),
+    "clipa_softce": (_I32, [_P, _I64, _I64, _I64, _P, _P, _P, _F, _F, _P, _P, _P, _I64, _I64, _P, _P]),
 }
 
 _lib = None

@@ -922,6 +922,91 @@ def color_jitter_u8_(img, apply=None, order=None, factors=None, gray_flags=None)
     return img
 
 
+def mixcut_u8(img, lam=None, box=None):
+    """Batch Mixup or CutMix in place on uint8 [B,3,S,S] in NCHW or channels_last memory (what DeviceAugment returns): sample b
+    is mixed with its mirror B-1-b (clipa_jax/transforms/mixup.py:141-201).  Exactly one of
+      lam f32 [B]                      mixup: out_b = lam_b x_b + (1 - lam_b) x_{B-1-b}, the fp32 byte arithmetic of csrc/mixcut.hip
+      box int32 [B,4] = (y0,y1,x0,x1)  cutmix: out_b = x_{B-1-b} inside the half-open box, x_b outside
+    on the device.  lam outside [0, 1] or NaN, a box outside the image or with y0 > y1 or x0 > x1: that pair is left as it was and
+    the call raises at the next check (check_token_ids, as for the other device-validated descriptors).  -> img."""
+    if (lam is None) == (box is None):
+        raise RuntimeError("clipa_amd.ops.mixcut_u8: give lam (mixup) or box (cutmix), not both")
+    if not img.is_cuda:
+        raise RuntimeError(f"clipa_amd.ops.mixcut_u8: img must live on the GPU (no CPU fallback); got {img.device}")
+    if img.dtype != u8 or img.dim() != 4 or img.shape[1] != 3 or img.shape[2] != img.shape[3]:
+        raise RuntimeError(f"clipa_amd.ops.mixcut_u8: expected uint8 [B,3,S,S], got {img.dtype} {tuple(img.shape)}")
+    B, S = img.shape[0], img.shape[2]
+    if img.is_contiguous():
+        nhwc = 0
+    elif img.is_contiguous(memory_format=torch.channels_last):
+        nhwc = 1
+    else:
+        raise RuntimeError("clipa_amd.ops.mixcut_u8: img must be dense in NCHW or channels_last memory (the operation is in place)")
+    if lam is not None:
+        _chk(lam, f32, "lam", 1)
+        if lam.numel() != B:
+            raise RuntimeError(f"clipa_amd.ops.mixcut_u8: lam must be f32 [{B}], got {tuple(lam.shape)}")
+        lam = lam.contiguous()
+    else:
+        _chk(box, torch.int32, "box", 2)
+        if tuple(box.shape) != (B, 4):
+            raise RuntimeError(f"clipa_amd.ops.mixcut_u8: box must be int32 [{B},4], got {tuple(box.shape)}")
+        box = box.contiguous()
+    if B == 0:
+        return img
+    check_token_ids()                                   # surfaces an earlier launch's rejected samples
+    err = _oob_counter(img.device)
+    with _Timed("mixcut", 0.0, 4.0 * (B // 2) * 3 * S * S):
+        lib.call("clipa_mixcut_u8", _p(img), _p(lam), _p(box), B, S, nhwc, 0 if lam is not None else 1, _p(err), _stream())
+    _oob_submit(err, "mixcut_u8", "samples rejected (lam outside [0, 1], or a box outside the image or with y0 > y1 / x0 > x1)")
+    return img
+
+
+SOFTCE_MAX_CLASSES = 32768      # csrc/softce.hip: SCE_MAX_C
+
+
+def soft_target_ce(logits, ya, yb=None, lam=None, smoothing=0.0, gscale=None, _max_workgroups=0):
+    """Soft-target cross-entropy rows in one pass (clipa_jax/losses/common.py:104-109 on the labels of transforms/mixup.py:203-211):
+    logits f32 [B, C] (a [B, C] view of a wider buffer is read in place: its other columns are never touched), ya int32 [B],
+    optional yb int32 [B] with lam f32 [B]; t_c = (1 - smoothing) (lam [c = ya] + (1 - lam) [c = yb]) + smoothing / C.
+    -> (loss f32 [B], lse f32 [B], dlogits): dlogits = gscale (softmax - t) as the bf16 [B, C] view of a [B, C rounded up to 8]
+    buffer whose other columns are zero, or None when gscale is None.  Fixed summation order: the same bits for every grid.
+    Labels outside [0, C) or lam outside [0, 1] raise at the next check (check_token_ids); such rows come back NaN."""
+    _chk(logits, f32, "logits", 2)
+    _chk(ya, torch.int32, "ya", 1)
+    B, C = logits.shape
+    if not 2 <= C <= SOFTCE_MAX_CLASSES:
+        raise RuntimeError(f"clipa_amd.ops.soft_target_ce: C = {C} classes; the kernel takes 2 to {SOFTCE_MAX_CLASSES}")
+    if (yb is None) != (lam is None):
+        raise RuntimeError("clipa_amd.ops.soft_target_ce: yb and lam come together")
+    vecs = [("ya", ya)]
+    if yb is not None:
+        _chk(yb, torch.int32, "yb", 1)
+        _chk(lam, f32, "lam", 1)
+        vecs += [("yb", yb), ("lam", lam)]
+    if any(t.numel() != B for _, t in vecs):
+        raise RuntimeError(f"clipa_amd.ops.soft_target_ce: {', '.join(n for n, _ in vecs)} must have B = {B} entries")
+    if not 0.0 <= float(smoothing) <= 1.0:
+        raise RuntimeError(f"clipa_amd.ops.soft_target_ce: smoothing = {smoothing} outside [0, 1]")
+    ya, yb, lam = (None if t is None else t.contiguous() for t in (ya, yb, lam))
+    ya, yb, lam = (t.clone() if t is not None and t.data_ptr() % 16 else t for t in (ya, yb, lam))
+    logits, ld = _aligned_rows(logits)
+    loss = torch.empty(B, device=logits.device, dtype=f32)
+    lse = torch.empty(B, device=logits.device, dtype=f32)
+    ldd = (C + 7) // 8 * 8
+    dl = torch.empty((B, ldd), device=logits.device, dtype=bf16) if gscale is not None else None
+    if B == 0:
+        return loss, lse, (dl[:, :C] if dl is not None else None)
+    check_token_ids()
+    err = _oob_counter(logits.device)
+    with _Timed("softce", 0.0, 4.0 * B * C + (2.0 * B * ldd if dl is not None else 0.0), f"{B},{C}"):
+        lib.call("clipa_softce", _p(logits), B, C, ld, _p(ya), _p(yb), _p(lam), float(smoothing),
+                 float(gscale) if gscale is not None else 0.0, _p(loss), _p(lse), _p(dl), ldd, int(_max_workgroups), _p(err),
+                 _stream())
+    _oob_submit(err, "soft_target_ce", "rows rejected (a label outside [0, C), or lam outside [0, 1] or NaN)")
+    return loss, lse, (dl[:, :C] if dl is not None else None)
+
+
 def assemble_tokens(patch, cls, pos, B, L):
     D = patch.shape[1]
     tok = torch.empty((B * L, D), device=patch.device, dtype=bf16)

@@ -551,6 +551,29 @@ int clipa_clip_coef(const float* acc, float max_norm, float* norm_out, float* co
  * all-to-all form of a reduce-scatter (scale = 1/W: DDP's gradient average).  bf16 or f32 in / out, fp32 sums in rank
  * order; n % 8 == 0. */
 int clipa_reduce_shards(const void* in, void* out, int64_t n, int W, int in_f32, int out_f32, float scale, void* stream);
+/* Image-tower fine-tuning (csrc/mixcut.hip, csrc/softce.hip).
+ * Batch Mixup / CutMix IN PLACE on uint8 [B,3,S,S] in NCHW (nhwc = 0) or channels_last (nhwc = 1) memory - replaces the image
+ * half of MixupAndCutmix, clipa_jax/transforms/mixup.py:141-201 with the box of transforms/random_erasing.py:25-61: sample b is
+ * mixed with its mirror B-1-b (tf.reverse, mixup.py:179,199).  mode 0 mixup, lam f32 [B]: out_b = lam_b x_b + (1 - lam_b)
+ * x_{B-1-b} per byte as d = a - b', t = lam d, v = t + b', out = (uint8)(int)(v + 0.5f) in fp32 without contraction (box
+ * unused, may be NULL).  mode 1 cutmix, box int32 [B][4] = (y0, y1, x0, x1) half-open, inside the image: out_b = x_{B-1-b}
+ * inside box_b and x_b outside (lam unused, may be NULL).  With odd B the middle sample is untouched.  Descriptors are validated
+ * on the device first: a pair with lam outside [0, 1] or NaN, or with a box outside the image or y0 > y1 or x0 > x1, is left as
+ * it was and counted in err_count (device int32, may be NULL).  S <= 4096, B <= 131070. */
+int clipa_mixcut_u8(void* img, const float* lam, const int32_t* box, int64_t B, int64_t S, int nhwc, int mode, int32_t* err_count,
+                    void* stream);
+/* Soft-target cross-entropy in one pass - replaces softmax_xent, clipa_jax/losses/common.py:104-109, on the mixed and smoothed
+ * labels of clipa_jax/transforms/mixup.py:203-211 without the [B, C] target matrix: logits f32 [B, ld], 2 <= C <= 32768 real
+ * columns (columns >= C are never read), ld % 4 == 0; ya int32 [B], yb int32 [B] with lam f32 [B] or both NULL (lam = 1);
+ *   t_c = (1 - smoothing) (lam [c = ya] + (1 - lam) [c = yb]) + smoothing / C;
+ *   lse[i] = log sum_c exp z_ic, loss[i] = lse[i] - sum_c t_c z_ic, and where dlogits is given
+ *   dlogits[i, c] = gscale (softmax(z_i)_c - t_c) as bf16 [B, ldd], ldd % 8 == 0, columns C .. ldd - 1 written as zero.
+ * One wave per row, fixed summation order (csrc/softce.hip), no float atomics: bit-identical for every max_workgroups (0 = one
+ * workgroup per four rows).  A label outside [0, C) or lam outside [0, 1] or NaN is counted in err_count (device int32, may be
+ * NULL): that row's loss and lse are NaN, its gradient row zero.  The mean of the row losses is a clipa_sum_scale launch. */
+int clipa_softce(const float* logits, int64_t B, int64_t C, int64_t ld, const int32_t* ya, const int32_t* yb, const float* lam,
+                 float smoothing, float gscale, float* loss, float* lse, void* dlogits, int64_t ldd, int64_t max_workgroups,
+                 int32_t* err_count, void* stream);
 
 #ifdef __cplusplus
 }
